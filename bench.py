@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json metric on MI355X: Groth16 proofs/s (BN254, 2^20 constraints, synthetic zkey/wtns =
-configs[1]) with G1-MSM Mscalar/s and NTT Melem/s as sub-metrics.
+configs[1]) with G1-MSM Mscalar/s and NTT Melem/s as sub-metrics (--full).
 
 A "step" is one whole proof: buildABC -> 3 x (iNTT, coset NTT) -> joinABC -> 5 MSMs -> blinding/toAffine, with the
 proving key AND the witness already resident in HBM when the timed region starts (zkmi_groth16_prove_dev).
 N > 1: one process per GPU (torchrun), every rank proves its own stream of proofs over a replicated key — the proof
 is the independent unit (SURVEY.md §8e "whole proofs"); no data-path collective; "scaling": "weak".
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0. Such a plain run sets up, warms up, times exactly K
+proofs and prints the headline; --dump-outputs DIR also writes the last timed proof. --full adds everything else the line has carried: repeated
+regions, stage / kernel times, sub-metrics, roofline, int_alu, the N-API wall, the CPU baselines with their parity checks, the box probes, the
+multi-rank extras and the other BASELINE configs.
 """
 import argparse
 import ctypes as C
@@ -50,18 +53,56 @@ def _oracle():
     return O
 
 
-def drain_c_stdout_to_stderr():
-    """RCCL prints its version banner through C stdio; with stdout redirected to a pipe or file that text sits in libc's buffer until exit
-    and would land AFTER the JSON line. Flush it to stderr so that stdout carries the one JSON line and nothing else."""
-    import ctypes
+_LINE_OUT = None
+
+
+def claim_stdout():
+    """Point fd 1 at stderr for the rest of the process and keep the original stdout for the result line alone. Native libraries write to fd 1
+    on their own (RCCL's version banner, flushed as soon as it is printed), and stdout must carry the one JSON line and nothing else."""
+    global _LINE_OUT
     sys.stdout.flush()
-    keep = os.dup(1)
-    try:
-        os.dup2(2, 1)
-        ctypes.CDLL(None).fflush(None)
-    finally:
-        os.dup2(keep, 1)
-        os.close(keep)
+    _LINE_OUT = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+
+
+def emit(line):
+    out = _LINE_OUT or sys.stdout
+    out.write(json.dumps(line) + "\n")
+    out.flush()
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array. Every value is an integer below 2^32 (a
+    32-bit word of a field element), so float64 holds it exactly."""
+    total = sum(a.size for a in arrays.values()) * 8
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than 64 MB")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+
+
+def _words(b, coords):
+    """affine point / field element bytes (little-endian) -> (coords, 32-bit words)"""
+    return np.frombuffer(bytes(b), "<u4").reshape(coords, -1)
+
+
+def proof_arrays(proof, public, n8):
+    """A PLONK / FFLONK proof object (decimal strings) -> {name: (elements, 32-bit words)}: every numeric entry, nested names joined by '_'."""
+    out = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}_{k}" if name else k, x)
+        elif isinstance(v, list) and v and all(isinstance(x, str) and x.isdigit() for x in v):
+            out[name] = _words(b"".join(int(x).to_bytes(n8, "little") for x in v), len(v))
+        elif isinstance(v, str) and v.isdigit():
+            out[name] = _words(int(v).to_bytes(n8, "little"), 1)
+    walk("", proof)
+    if public:
+        out["public_signals"] = _words(b"".join(int(x).to_bytes(n8, "little") for x in public), len(public))
+    return out
 
 
 def box_calibration(L):
@@ -135,11 +176,9 @@ def reference_wasm_baseline():
 
 
 def _ref_bundle():
-    """the reference's bundle where a box has it: the staged copy oracle/_ref (make -C oracle _ref; git-ignored, shipped by gpurun), else /root/reference"""
-    for p in (os.path.join(ROOT, "oracle", "_ref", "build", "snarkjs.min.js"), "/root/reference/build/snarkjs.min.js"):
-        if os.path.exists(p):
-            return p
-    return None
+    """the reference's bundle where a box has it: the staged copy oracle/_ref (make -C oracle _ref; git-ignored, staged by build() where the reference is present)"""
+    p = os.path.join(ROOT, "oracle", "_ref", "build", "snarkjs.min.js")
+    return p if os.path.exists(p) else None
 
 
 def reference_wasm_same_box(proto, cases, curve="bn128", budget_s=200.0, warm=None):
@@ -383,7 +422,7 @@ def other_configs(args):
         if left < expect_s:
             res[tag] = {"skipped": f"budget: {left:.0f} s left (--other-configs-budget {args.other_configs_budget:.0f} / --total-budget {args.total_budget:.0f}), this config needs ~{expect_s:.0f} s (key synthesis + load + proofs + its reference leg)"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-other-configs"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-other-configs"] + extra
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.no_ref_wasm:
@@ -477,11 +516,14 @@ def bench_plonk(args, rank, world, dist, torch):
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
+    # fixed blinding draws (the Fr.random() values of the reference's prover): the same arguments prove the same proofs, run after run
+    nd = 9 if proto == "fflonk" else 11
+    draws = [bytes(key.f.mont(4242 + 17 * i)) for i in range(nd)]
     for _ in range(args.warmup):
-        plonk.prove(key, wtns)
+        plonk.prove(key, wtns, blinding_mont=draws)
     two = args.pipeline == 2 and hasattr(plonk, "prove_many")          # throughput mode: two proofs in flight from this one host thread
     if two:
-        plonk.prove_many(key, [wtns, wtns])                             # size the second slot's buffers outside the timed region
+        plonk.prove_many(key, [wtns, wtns], [draws, draws])             # size the second slot's buffers outside the timed region
     per_proof = []
     import gc
     gc.collect()
@@ -489,22 +531,22 @@ def bench_plonk(args, rank, world, dist, torch):
     barrier()
     t0 = time.perf_counter()
     if two:
-        res = plonk.prove_many(key, [wtns] * args.steps)[-1]            # EXACTLY args.steps whole proofs
+        res = plonk.prove_many(key, [wtns] * args.steps, [draws] * args.steps)[-1]     # EXACTLY args.steps whole proofs
     else:
         for _ in range(args.steps):
             tp = time.perf_counter()
-            res = plonk.prove(key, wtns)
+            res = plonk.prove(key, wtns, blinding_mont=draws)
             per_proof.append(time.perf_counter() - tp)
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
     lat = []
-    for _ in range(6 if two else 0):                                    # single-proof latency beside the throughput figure
+    for _ in range(6 if two and args.full else 0):                      # single-proof latency beside the throughput figure
         tl = time.perf_counter()
         plonk.prove(key, wtns)
         lat.append(time.perf_counter() - tl)
     lat_up = []
-    for _ in range(4 if wtns is not wtns_host else 0):                  # the same with the witness parsed and uploaded per proof (32 MB at 2^20 over PCIe)
+    for _ in range(4 if wtns is not wtns_host and args.full else 0):    # the same with the witness parsed and uploaded per proof (32 MB at 2^20 over PCIe)
         tl = time.perf_counter()
         plonk.prove(key, wtns_host)
         lat_up.append(time.perf_counter() - tl)
@@ -513,6 +555,19 @@ def bench_plonk(args, rank, world, dist, torch):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
+        out = {
+            "metric": f"{proto}_proofs_per_sec", "value": round(world * args.steps / elapsed, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u32", "data": "synthetic",
+            "config": {"workload": f"BN254 {proto.upper()} prove, 2^{lg} constraints, synthetic valid key" + (" (BASELINE configs[3])" if proto == "plonk" else "") + "; key " + ("and witness resident" if wtns is not wtns_host else "resident, witness uploaded per proof"),
+                       "curve": "bn128", "log_n": lg, "n_constraints": int(key.nConstraints), "n_additions": int(key.nAdditions),
+                       "additions": f"{args.plonk_additions} addition gate(s) per multiplication gate, internal signals in chains of that depth (plonk_setup.js reduceCoefs on an `x^2 + b` circuit gives 1); calculateAdditions (plonk_prove.js:174-204) runs on the device INSIDE every timed proof",
+                       "parallelism": f"replica x{world}"},
+            "proofs_in_flight": 2 if two else 1, "host_gc": "Python's cyclic collector is off inside the timed region (timeit's convention)", "timed_region_ms_per_proof": [round(x * 1e3, 2) for x in per_proof],
+            "public_signal": res["publicSignals"][0][:24] + "..."}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, proof_arrays(res["proof"], res["publicSignals"], 32))
+    if rank == 0 and args.full:
         n = 1 << lg
         # dominant kernel of a PLONK proof: the bucket accumulations of the commitments (G1 MSMs against the resident SRS table);
         # job slot 0 holds the last one (n + O(1) terms). Live HIP-event time around that launch on the library stream.
@@ -541,26 +596,13 @@ def bench_plonk(args, rank, world, dist, torch):
             roof = {"bound": "hbm", "kernel": kname + " (last commitment, n terms)", "achieved": round(alg / (acc_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS,
                     "unit": "GB/s", "frac": round(alg / (acc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6), "traffic": pmc_traffic(f"{proto}:bn128:2^{lg}:additions={int(key.nAdditions)}", kname), "kernel_ms": round(acc_ms, 4), "algorithmic_bytes": alg,
                     "note": "integer-ALU-bound (256-bit Montgomery carry chains, no MFMA); traffic: average over the accumulation launches of a proof (9 commitments of n .. n + 6 terms)"}
-        out = {
-            "metric": f"{proto}_proofs_per_sec", "value": round(world * args.steps / elapsed, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u32", "data": "synthetic",
-            "config": {"workload": f"BN254 {proto.upper()} prove, 2^{lg} constraints, synthetic valid key" + (" (BASELINE configs[3])" if proto == "plonk" else "") + "; key " + ("and witness resident" if wtns is not wtns_host else "resident, witness uploaded per proof"),
-                       "curve": "bn128", "log_n": lg, "n_constraints": int(key.nConstraints), "n_additions": int(key.nAdditions),
-                       "additions": f"{args.plonk_additions} addition gate(s) per multiplication gate, internal signals in chains of that depth (plonk_setup.js reduceCoefs on an `x^2 + b` circuit gives 1); calculateAdditions (plonk_prove.js:174-204) runs on the device INSIDE every timed proof",
-                       "parallelism": f"replica x{world}"},
-            "roofline": roof, "int_alu": int_alu,
-            "proofs_in_flight": 2 if two else 1, "host_gc": "Python's cyclic collector is off inside the timed region (timeit's convention)", "latency_ms_single_proof": round(min(lat) * 1e3, 3) if lat else None, "latency_ms_serial_proofs": [round(x * 1e3, 2) for x in lat], "timed_region_ms_per_proof": [round(x * 1e3, 2) for x in per_proof],
-            "latency_ms_with_witness_upload": [round(x * 1e3, 2) for x in lat_up],
-            "public_signal": res["publicSignals"][0][:24] + "..."}
+        out.update({"roofline": roof, "int_alu": int_alu, "latency_ms_single_proof": round(min(lat) * 1e3, 3) if lat else None, "latency_ms_serial_proofs": [round(x * 1e3, 2) for x in lat],
+                    "latency_ms_with_witness_upload": [round(x * 1e3, 2) for x in lat_up]})
         same_box = None
         if world == 1 and not args.no_cpu_baseline and not args.no_ref_wasm:
             # the reference's own prover on this box's host cores at bounded domains (a reference PLONK proof at 2^20 takes minutes: mostly single-threaded
             # JS loops), its proofs for the same draws compared with the device's; scaled linearly to the bench size and labelled as such
             mod = fflonk if proto == "fflonk" else plonk
-            nd = 9 if proto == "fflonk" else 11
-            fld = plonk._Field(0) if hasattr(plonk, "_Field") else fflonk._Field(0)
-            draws = [bytes(fld.mont(4242 + 17 * i)) for i in range(nd)]
             cases = []
             for l2 in sorted({min(14, lg), min(16, lg)}):
                 zk2, wt2 = (synth_plonk.make_fflonk(l2, seed=3, additions=args.plonk_additions) if proto == "fflonk" else synth_plonk.make("bn128", l2, seed=3, additions=args.plonk_additions))
@@ -599,12 +641,11 @@ def bench_plonk(args, rank, world, dist, torch):
                                    "parity_on_sample": bool(got["proof"] == ref_proof), "reference_wasm": reference_wasm_baseline_plonk(proto, lg)}
             _plonk_same_box_into(out["cpu_baseline"], same_box, proto, lg)
         out["box_calibration"] = box_calibration(zkmi.lib())
-        drain_c_stdout_to_stderr()
-        print(json.dumps(out), flush=True)
+    if rank == 0:
+        emit(out)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-        drain_c_stdout_to_stderr()
 
 
 def multi_rank_extras(args, rank, world, dist, torch, barrier, cid, q8, lg, r_m, s_m, zkey, wtns, proof_pts):
@@ -783,12 +824,10 @@ def preflight(args, rank, local_rank, world, dist, torch):
         out = {"preflight": True, "n_gpus": world, "world_size_rccl": dist.get_world_size() if dist is not None else 1, "backend": dist.get_backend() if dist is not None else None,
                "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "ranks": gathered, "ok": bool(ok and all(g is not None for g in gathered)),
                "distinct_devices": len({(g or {}).get("device") for g in gathered}) == world}
-        drain_c_stdout_to_stderr()
-        print(json.dumps(out), flush=True)
+        emit(out)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-        drain_c_stdout_to_stderr()
 
 
 def main():
@@ -802,7 +841,7 @@ def main():
     ap.add_argument("--no-napi-wall", action="store_true")
     ap.add_argument("--pipeline", type=int, default=2, choices=[1, 2], help="proofs in flight per GPU (2: the tail of proof k overlaps the front of proof k+1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=3, help="how often the timed region is run (value = the first; min / median / max of all reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="how often the timed region is run (value = the first; min / median / max of all reported); default 3 with --full, else 1")
     ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs[4] / [3] / [2] (child runs after the headline line; default run at N = 1 only)")
     ap.add_argument("--other-configs-budget", type=float, default=330.0, help="wall-clock seconds the other configs may take together")
     ap.add_argument("--total-budget", type=float, default=335.0, help="wall-clock seconds the whole default run may take (headline + other configs); a config that does not fit is reported as skipped")
@@ -821,14 +860,19 @@ def main():
     ap.add_argument("--napi-wall-reps", type=int, default=5)
     ap.add_argument("--preflight", action="store_true", help="every rank reports its device ordinal, free HBM, the peer-access row of its device and the RCCL world, rank 0 prints ONE JSON line, nothing is proved: "
                     "cheap first contact with a multi-GPU node before the real run")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the spread over repeated timed regions, stage / kernel times and single-proof latency, "
+                    "the pipelined == serial proof check, sub-metrics, roofline and int_alu, the N-API wall, the CPU baselines with their parity checks, the box probes, the "
+                    "multi-rank extras and the other BASELINE configs; a plain run sets up, warms up, times --steps proofs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed proof returned as DIR/<name>.npy (float64; 32-bit words of the field elements)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     relaunch_if_needed(args)
+    claim_stdout()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if rank != 0:
-        os.dup2(2, 1)                                       # only rank 0 owns stdout (the one JSON line)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP backend has no CPU fallback")
@@ -905,22 +949,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         region_s = [float(x) for x in t.tolist()]
         region_s[0] = elapsed                               # reduced below with the historical code path
-    # stage / kernel times and single-proof latency: a few serial proofs after the timed region
-    lat = []
-    for _ in range(4):
-        tl = time.perf_counter()
-        serial_pts = step()
-        lat.append(time.perf_counter() - tl)
-        for k, v in pk.stage_ms().items():
-            stage_acc[k] = stage_acc.get(k, 0.0) + v / 4 * args.steps
-        for k in range(5):
-            accum_ms[k].append(L.zkmi_msm_accum_ms(k))
-    assert all(np.array_equal(a, b) for a, b in zip(serial_pts, proof_pts)), "pipelined and serial proofs differ"
-    # mixed additions per accumulation launch, counted ON THE DEVICE from the digit lists of one more serial proof (zkmi_msm_stats)
-    zkmi.check(L.zkmi_msm_stats(1))
-    step()
-    additions = {k: L.zkmi_msm_accum_additions(k) for k in range(5)}
-    zkmi.check(L.zkmi_msm_stats(0))
+    lat, additions = [], {}
+    if args.full:
+        # stage / kernel times and single-proof latency: a few serial proofs after the timed region
+        for _ in range(4):
+            tl = time.perf_counter()
+            serial_pts = step()
+            lat.append(time.perf_counter() - tl)
+            for k, v in pk.stage_ms().items():
+                stage_acc[k] = stage_acc.get(k, 0.0) + v / 4 * args.steps
+            for k in range(5):
+                accum_ms[k].append(L.zkmi_msm_accum_ms(k))
+        assert all(np.array_equal(a, b) for a, b in zip(serial_pts, proof_pts)), "pipelined and serial proofs differ"
+        # mixed additions per accumulation launch, counted ON THE DEVICE from the digit lists of one more serial proof (zkmi_msm_stats)
+        zkmi.check(L.zkmi_msm_stats(1))
+        step()
+        additions = {k: L.zkmi_msm_accum_additions(k) for k in range(5)}
+        zkmi.check(L.zkmi_msm_stats(0))
     if dist is not None:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -931,7 +976,7 @@ def main():
     # RCCL reduce"): every rank runs the device Pippenger on its slice, one all_gather of the partial points, local fold.
     sharded = None
     extras_failed = False
-    if dist is not None:
+    if dist is not None and args.full:
         # The replica metric above is complete at this point; the multi-rank extras below must never cost the line: any error in them is
         # reported inside the line and the process then leaves without further collectives.
         try:
@@ -942,6 +987,24 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "groth16_proofs_per_sec", "value": round(world * args.steps / elapsed, 4), "unit": "proofs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "pipeline_depth": args.pipeline,
+            "repeats": (lambda v: {"what": f"the timed region ({args.steps} proofs between two barriers) run {len(v)} times back to back; `value` is the FIRST; proofs/s over all ranks",
+                                   "proofs_per_s": [round(x, 3) for x in v], "min": round(min(v), 3), "median": round(float(np.median(v)), 3), "max": round(max(v), 3)})(
+                [world * args.steps / x for x in ([elapsed] + region_s[1:])]),
+            "config": {"workload": f"{'BN254' if cid == 0 else 'BLS12-381'} Groth16 prove, 2^{lg} constraints, synthetic zkey/wtns (BASELINE configs[{1 if (cid == 0 and lg == 20) else (2 if cid == 0 else 4)}]), "
+                                   + (f"B density {1.0 if not args.b_zero_every else round(1 - 1 / args.b_zero_every, 3)} ({'every section dense, SURVEY 8d recipe' if not args.b_zero_every else f'every {args.b_zero_every}-th B1/B2 base at infinity'}), "
+                                      if args.coef_dist == "flat" else "circuit-shaped coefficient section (heavy-tailed rows up to 10^5 terms, see coef_layout), B density 0.4, ")
+                                   + f"{args.witness} witness; key + witness resident in HBM",
+                       "curve": args.curve, "log_n": lg, "n_vars": zk["nVars"], "n_coef": int((zk['coeffs'].size - 4) // 44), "witness": args.witness, "coef_dist": args.coef_dist, "b_density": 0.4 if args.coef_dist == "real" else (1.0 if not args.b_zero_every else round(1 - 1 / args.b_zero_every, 4)),
+                       "parallelism": f"replica x{world} (one proof stream per GPU, {args.pipeline} proof(s) in flight)"},
+        }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"pi_a": _words(proof_pts[0], 2), "pi_b": _words(proof_pts[1], 4), "pi_c": _words(proof_pts[2], 2)})
+    if rank == 0 and args.full:
         # ---- sub-metrics (outside the timed region): G1 MSM and NTT at the same size, device-event time ----
         n = 1 << lg
         d_b = zkmi.DeviceBuffer(n * 2 * q8)
@@ -1005,20 +1068,8 @@ def main():
             wrate = adds * vpa / 64 / (acc[dom] * 1e-3) / 1e9
             int_alu["valu_issue"] = {"valu_instr_per_addition": vpa, "achieved": round(wrate, 1), "peak": VALU_ISSUE_PEAK_G, "unit": "G wave-instr/s", "frac": round(wrate / VALU_ISSUE_PEAK_G, 4),
                                      "note": "VALU instructions of the main path of one mixed addition (tools/isa_counts.py) x additions / 64 / launch time against one wave instruction per SIMD every 4 cycles; the G2 kernels (r06) hold one Fq2 component per lane in registers, two lanes per addition (their counts are per addition: BN254 2 x 3 360 at 3 waves per SIMD, BLS12-381 2 x 7 431 at 2 waves per SIMD), where a dependent v_mad_u64_u32 chain reaches 0.82 - 0.9 of that peak (tools/fieldbench29: wps=2)"}
-        out = {
-            "metric": "groth16_proofs_per_sec", "value": round(world * args.steps / elapsed, 4), "unit": "proofs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "pipeline_depth": args.pipeline, "latency_ms_single_proof": round(float(np.median(lat)) * 1e3, 3),
-            "repeats": (lambda v: {"what": f"the timed region ({args.steps} proofs between two barriers) run {len(v)} times back to back; `value` is the FIRST; proofs/s over all ranks",
-                                   "proofs_per_s": [round(x, 3) for x in v], "min": round(min(v), 3), "median": round(float(np.median(v)), 3), "max": round(max(v), 3)})(
-                [world * args.steps / x for x in ([elapsed] + region_s[1:])]),
-            "config": {"workload": f"{'BN254' if cid == 0 else 'BLS12-381'} Groth16 prove, 2^{lg} constraints, synthetic zkey/wtns (BASELINE configs[{1 if (cid == 0 and lg == 20) else (2 if cid == 0 else 4)}]), "
-                                   + (f"B density {1.0 if not args.b_zero_every else round(1 - 1 / args.b_zero_every, 3)} ({'every section dense, SURVEY 8d recipe' if not args.b_zero_every else f'every {args.b_zero_every}-th B1/B2 base at infinity'}), "
-                                      if args.coef_dist == "flat" else "circuit-shaped coefficient section (heavy-tailed rows up to 10^5 terms, see coef_layout), B density 0.4, ")
-                                   + f"{args.witness} witness; key + witness resident in HBM",
-                       "curve": args.curve, "log_n": lg, "n_vars": m, "n_coef": int((zk['coeffs'].size - 4) // 44), "witness": args.witness, "coef_dist": args.coef_dist, "b_density": 0.4 if args.coef_dist == "real" else (1.0 if not args.b_zero_every else round(1 - 1 / args.b_zero_every, 4)),
-                       "parallelism": f"replica x{world} (one proof stream per GPU, {args.pipeline} proof(s) in flight)"},
+        out.update({
+            "latency_ms_single_proof": round(float(np.median(lat)) * 1e3, 3),
             "submetrics": {"g1_msm_mscalar_per_s": round(n / msm_ms / 1e3, 2), "g1_msm_ms": round(msm_ms, 4),
                            "g1_msm_resident_tables_mscalar_per_s": round(n / msm_tab_ms / 1e3, 2), "g1_msm_resident_tables_ms": round(msm_tab_ms, 4),
                            "g1_msm_note": "g1_msm_*: zkmi_msm_dev on caller-owned plain bases (R-form): the library's R'-form copy and its conversion pass are inside the time, sort / accumulate / reduce on one stream (r04 measured the MSM in 2 and 4 pieces with the sorts underneath the accumulations: slower, profiles/NOTES.md); resident_tables: the same MSM over pre-computed window tables (how a key holds its bases)",
@@ -1031,7 +1082,7 @@ def main():
             "accum_mixed_additions": {names[k][0]: int(v) for k, v in additions.items()},
             "roofline": roof,
             "int_alu": int_alu,
-        }
+        })
         out["coef_layout"] = dict(pk.coef_layout(), note="the resident coefficient section: rows cut into segments of <= 32 terms, sorted by length into slices of 64 (csrc/groth16.hip); cut_rows = rows beyond 32 terms")
         if world == 1 and not args.no_napi_wall:
             # SURVEY.md 8d timing protocol: wall time THROUGH the N-API call with host buffers (H2D of inputs, D2H of results inside); the key is opened by
@@ -1054,18 +1105,17 @@ def main():
                 got = pk_s.prove_raw(binfile.read_wtns(wt_s)["witness"], rs, ss)
                 out["cpu_baseline"]["parity_on_sample"] = bool(all(np.array_equal(a, b) for a, b in zip(got, ref)))
                 pk_s.release()
-    if out is not None:
+    if out is not None and args.full:
         out["box_calibration"] = box_calibration(L)
-    if out is not None and world == 1 and not args.no_other_configs and args.curve == "bn128" and lg == 20 and args.coef_dist == "flat":
+    if out is not None and args.full and world == 1 and not args.no_other_configs and args.curve == "bn128" and lg == 20 and args.coef_dist == "flat":
         # BASELINE configs[4], [3], [2] inside the same driver run, after everything above: this process's key and buffers are released first
         pk.release(); d_w.free()
         out["other_configs"] = other_configs(args)
     if dist is not None and not extras_failed:
         dist.barrier()
         dist.destroy_process_group()
-    drain_c_stdout_to_stderr()                   # every rank: nothing but rank 0's JSON line may reach stdout
     if out is not None:
-        print(json.dumps(out), flush=True)       # the ONE JSON line, after everything else this process may write
+        emit(out)                                # the ONE JSON line, after everything else this process may write
     if extras_failed:
         sys.stdout.flush(); sys.stderr.flush()
         os._exit(0)                              # the communicator may be unusable: no teardown collectives

@@ -34,3 +34,20 @@ def test_pmc_traffic_is_looked_up_per_workload():
     # a workload that was never counted gets no figure from another one
     assert bench.pmc_traffic("groth16:bn128:2^16:b_zero_every=0:uniform", "k_msm_accum29_g2s<Bn254Fq>") is None
     assert bench.pmc_traffic("groth16:bn128:2^20:b_zero_every=3:uniform", "k_msm_accum29_g2s<Bn254Fq>") is None
+
+
+def test_dump_outputs_hold_every_word_exactly(tmp_path):
+    """--dump-outputs: field elements go out as float64 32-bit words that give the element back bit for bit; a dump beyond 64 MB is refused"""
+    import numpy as np
+    import pytest
+    bench = importlib.import_module("bench")
+    x, y = 21888242871839275222246405745257275088696311157297823662689037894645226208582, 2 ** 253 + 12345
+    arrays = bench.proof_arrays({"A": [str(x), str(y), "1"], "eval_a": str(y), "protocol": "plonk", "nested": {"T": [str(x)]}}, ["7"], 32)
+    assert set(arrays) == {"A", "eval_a", "nested_T", "public_signals"} and arrays["A"].shape == (3, 8) and arrays["eval_a"].shape == (1, 8)
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    a = np.load(tmp_path / "out" / "A.npy")
+    assert a.dtype == np.float64
+    assert [int.from_bytes(row.astype("<u4").tobytes(), "little") for row in a] == [x, y, 1]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((8 << 20) + 1)})
+    assert not (tmp_path / "big").exists()

@@ -15,9 +15,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ADDON = os.path.join(ROOT, "snarkjs_amd", "napi", "zkmi_napi.node")
 NODE = shutil.which("node")
-# the reference's bundle: /root/reference in the build container, or its staged copy oracle/_ref/ (make -C oracle _ref; git-ignored, travels with gpurun)
-BUNDLE = next((p for p in (os.path.join(ROOT, "oracle", "_ref", "build", "snarkjs.min.js"), "/root/reference/build/snarkjs.min.js") if os.path.exists(p)), None)
-need_bundle = pytest.mark.skipif(BUNDLE is None, reason="reference bundle not present: run `make -C oracle _ref` where /root/reference exists")
+# the reference's bundle: its copy staged into oracle/_ref/ by build() (make -C oracle _ref; git-ignored) where the reference is present
+BUNDLE = os.path.join(ROOT, "oracle", "_ref", "build", "snarkjs.min.js")
+BUNDLE = BUNDLE if os.path.exists(BUNDLE) else None
+need_bundle = pytest.mark.skipif(BUNDLE is None, reason="reference bundle not staged: run `make -C oracle _ref` where the reference is present")
 need_node = pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the built addon is missing")
 FLAGS = ["--harmony-optional-chaining", "--harmony-nullish"]
 

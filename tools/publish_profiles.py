@@ -32,10 +32,10 @@ def stats_md(csv_path, out, cmd):
             f.write(f"| `{r['Name'].split('(')[0].replace('void ', '')[:90]}` | {r['Calls']} | {float(r['AverageNs'])/1e3:.1f} | {float(r['TotalDurationNs'])/1e6:.2f} | {float(r['Percentage']):.2f} |\n")
 
 
-for sub, name, cmd in (("stats", "bench_kernel_stats", "python bench.py --steps 20 --warmup 3 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
-                       ("stats_bls", "bench_bls12381_kernel_stats", "python bench.py --curve bls12381 --steps 6 --warmup 2 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
-                       ("stats_real", "bench_real_kernel_stats", "python bench.py --coef-dist real --witness mixed --steps 10 --warmup 2 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
-                       ("stats_p24", "bench_p24_kernel_stats", "python bench.py --log-n 24 --steps 3 --warmup 1 --pipeline 1 --no-cpu-baseline --no-napi-wall")):
+for sub, name, cmd in (("stats", "bench_kernel_stats", "python bench.py --full --steps 20 --warmup 3 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
+                       ("stats_bls", "bench_bls12381_kernel_stats", "python bench.py --full --curve bls12381 --steps 6 --warmup 2 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
+                       ("stats_real", "bench_real_kernel_stats", "python bench.py --full --coef-dist real --witness mixed --steps 10 --warmup 2 --pipeline 1 --no-cpu-baseline --no-napi-wall"),
+                       ("stats_p24", "bench_p24_kernel_stats", "python bench.py --full --log-n 24 --steps 3 --warmup 1 --pipeline 1 --no-cpu-baseline --no-napi-wall")):
     c = glob.glob(f"{src}/{sub}/**/*kernel_stats.csv", recursive=True)
     if c:
         stats_md(c[0], f"{dst}/{tag}_{name}_summary.md", cmd)
@@ -129,7 +129,7 @@ if fc and wc:
     json.dump(out, open(f"{dst}/pmc_traffic.json", "w"), indent=1, sort_keys=True)
     shutil.copy(f"{dst}/pmc_traffic.json", f"{dst}/{tag}_pmc_traffic.json")
     with open(f"{dst}/{tag}_pmc_traffic.md", "w") as f:
-        f.write(f"# HBM traffic per launch, accumulation kernels ({tag}; rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, `bench.py --steps 2 --warmup 1 --pipeline 1`)\n\n"
+        f.write(f"# HBM traffic per launch, accumulation kernels ({tag}; rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, `bench.py --full --steps 2 --warmup 1 --pipeline 1`)\n\n"
                 "FETCH_SIZE tallies memory-side read requests at 64 B each (`r02_gather_calibration.md`): exact for the 64-byte gathers of a G1 table entry and for the sector\n"
                 "behind a 16-byte list read, half the bytes of a 128-byte G2 gather by one lane. Correction per access class: G1 bytes = raw; G2 bytes = raw + (1 - tallied\n"
                 f"fraction) x 128 B x gathers (= mixed additions counted on the device: {g2_adds}); r06: k_msm_accum29_g2s reads an entry as 2 x 32 bytes in each of two\n"
@@ -203,7 +203,7 @@ if workloads:
     shutil.copy(f"{dst}/pmc_traffic.json", f"{dst}/{tag}_pmc_traffic.json")
     with open(f"{dst}/{tag}_pmc_traffic_other_configs.md", "w") as f:
         f.write(f"# HBM traffic per launch of the accumulation kernels, the other configs of the driver line ({tag}; rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes,\n"
-                "`bench.py <config> --steps 2 --warmup 1 --pipeline 1`). Corrected per access class with this round's gather calibration (" + f"{tag}_gather_calibration.md).\n\n"
+                "`bench.py --full <config> --steps 2 --warmup 1 --pipeline 1`). Corrected per access class with this round's gather calibration (" + f"{tag}_gather_calibration.md).\n\n"
                 "| workload | kernel | FETCH raw MB | WRITE MB | corrected total MB |\n|---|---|---|---|---|\n")
         for wl, k, raw, wr, tot in md_rows:
             f.write(f"| {wl} | `{k}` | {raw/1e6:.0f} | {wr/1e6:.0f} | {tot/1e6:.0f} |\n")
