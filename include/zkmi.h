@@ -232,6 +232,18 @@ int zkmi_pipeline_active(void);
 int zkmi_groth16_submit(uint64_t zkey_cache_key, const uint8_t* witness, size_t witness_len, int slot);
 int zkmi_groth16_collect(uint64_t zkey_cache_key, int slot, const uint8_t* r_mont, const uint8_t* s_mont, uint8_t* pi_a, uint8_t* pi_b, uint8_t* pi_c);
 int zkmi_groth16_release(uint64_t zkey_cache_key);
+/* groth16Verify (src/groth16_verify.js:26-87) for batches of proofs against one verifying key, on the device, one verdict per proof.
+ * zkmi_groth16_vk_load takes the key's points as the reference's fromObject reads them: (x, y, z) triples in standard form, little-endian,
+ * n8q bytes per Fq (Fq2 = c0 | c1); z = 0 infinity, z = 1 affine, other z Jacobian. ic_xyz holds nPublic + 1 points (IC[0..nPublic]).
+ * zkmi_groth16_verify_batch: proofs_xyz = n records pi_a (3 Fq) | pi_b (3 Fq2) | pi_c (3 Fq); publics = n x n_signals x 32 bytes,
+ * little-endian integers (the first n_signals IC points are used; n_signals > nPublic is an error, where the reference throws).
+ * verdicts[i]: 1 valid ("OK!"), 0 pairing check failed ("Invalid proof"), -1 a public input >= r ("Public inputs are not valid."),
+ * -2 a proof point not on the curve ("Proof commitments are not valid."). The verifier has its own stream and buffers: it never
+ * touches the pipeline slots of the provers. */
+int zkmi_groth16_vk_load(int curve, const uint8_t* alpha1_xyz, const uint8_t* beta2_xyz, const uint8_t* gamma2_xyz, const uint8_t* delta2_xyz,
+                         const uint8_t* ic_xyz, uint32_t n_public, uint64_t* vk_handle);
+int zkmi_groth16_verify_batch(uint64_t vk_handle, const uint8_t* proofs_xyz, const uint8_t* publics, uint32_t n_signals, size_t n, int8_t* verdicts);
+int zkmi_groth16_vk_release(uint64_t vk_handle);
 /* Multi-GPU proof (BASELINE configs[2]: MSMs sharded across the GPUs of a node). Every rank loads the shard of the
  * key that holds the witness-side bases of the variables [var_lo, var_hi) (sections 5-8) and the H bases [h_lo, h_hi) (section 9);
  * the section pointers of `zkey` are those of the FULL sections, the library slices them. zkmi_groth16_sums_dev runs the device

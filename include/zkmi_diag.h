@@ -67,6 +67,13 @@ unsigned long long zkmi_msm_dev_fallbacks(void);
  * out[0..5) = coefficient records, segments (<= 32 terms each), rows cut into several segments, partial-sum slots, padded terms held. */
 int zkmi_groth16_coef_layout(uint64_t zkey_cache_key, uint64_t* out, int n);
 
+/* Reduced pairing e(P_i, Q_i) (the curve.pairing of ffjavascript that src/groth16_verify.js:66-74 compares through pairingEq) of n pairs,
+ * for tests and debugging: g1_xyz n x 3 Fq, g2_xyz n x 3 Fq2 in the (x, y, z) form of zkmi_groth16_vk_load; out_f12 n x 12 Fq, standard form,
+ * the coefficients of w^0..w^11 in Fq[w]/(w^12 - 2s w^6 + s^2 + 1), xi = s + u (oracle/groth16_verify_oracle.py). A point at infinity gives 1. */
+int zkmi_pairing_dev(int curve, const uint8_t* g1_xyz, const uint8_t* g2_xyz, size_t n, uint8_t* out_f12);
+/* Device time of the verification kernel of the last zkmi_groth16_verify_batch, in milliseconds (HIP events on the verifier's stream); -1: none yet. */
+double zkmi_groth16_verify_last_ms(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,10 +252,12 @@ function installFused(snarkjs, options) {
     const g16 = (zkey, wtns, logger, o) => (single(o) ? orig.groth16.prove(zkey, wtns, logger, o) : prover.prove(zkey, wtns));
     const pl = (zkey, wtns, logger, o) => (single(o) ? orig.plonk.prove(zkey, wtns, logger, o) : polyProve(plonkN, plonkN.PlonkKey, 11, zkey, wtns));
     const ff = (zkey, wtns, logger, o) => (single(o) ? orig.fflonk.prove(zkey, wtns, logger, o) : polyProve(fflonkN, fflonkN.FflonkKey, 9, zkey, wtns));
-    snarkjs.groth16 = Object.freeze(Object.assign({}, orig.groth16, { prove: g16, fullProve: fullOf(g16) }));
+    // options.verify: snarkjs.groth16.verify on the device as well (js/groth16_verify_native.js: batches of concurrent calls, keys per vk content)
+    const verifier = options && options.verify ? require("./groth16_verify_native.js").makeVerifier(snarkjs, options) : null;
+    snarkjs.groth16 = Object.freeze(Object.assign({}, orig.groth16, { prove: g16, fullProve: fullOf(g16) }, verifier ? { verify: verifier.verify } : {}));
     snarkjs.plonk = Object.freeze(Object.assign({}, orig.plonk, { prove: pl, fullProve: fullOf(pl) }));
     snarkjs.fflonk = Object.freeze(Object.assign({}, orig.fflonk, { prove: ff, fullProve: fullOf(ff) }));
-    snarkjs.__zkmiFused = { orig, prover, keys };
+    snarkjs.__zkmiFused = { orig, prover, keys, verifier };
     return snarkjs.__zkmiFused;
 }
 async function uninstallFused(snarkjs) {
@@ -265,6 +267,7 @@ async function uninstallFused(snarkjs) {
     delete snarkjs.__zkmiFused;
     for (const k of st.keys.values()) { try { k.release(); } catch (e) { /* already released */ } }
     st.keys.clear();
+    if (st.verifier) st.verifier.release();
     await st.prover.release();
 }
 

@@ -133,7 +133,7 @@ typedef struct {
     napi_deferred deferred;
     napi_ref keep[8]; int n_keep;          /* arguments and result kept alive while the job runs */
     napi_ref result;                       /* value the promise resolves to (NULL: undefined) */
-    int kind;                              /* 0 msm, 1 ntt, 2 groth16Prove, 3 groth16Submit, 4 groth16Collect, 5 groth16Load, 6 msmTableMultiDev, 7 synchronize */
+    int kind;                              /* 0 msm, 1 ntt, 2 groth16Prove, 3 groth16Submit, 4 groth16Collect, 5 groth16Load, 6 msmTableMultiDev, 7 synchronize, 8 groth16Verify */
     double handle; const void* dptr[4]; size_t dk[4]; int dcnt;      /* kind 6: table handle, device scalars, term counts */
     int32_t slot;
     int32_t curve, group, logn, inverse;
@@ -153,6 +153,7 @@ static int job_run(job_t* j) {
     case 3: return zkmi_groth16_submit((uint64_t)j->key, j->a.ptr[0], j->a.len[0], j->slot);
     case 4: return zkmi_groth16_collect((uint64_t)j->key, j->slot, j->first, j->inc, j->o0, j->o1, j->o2);
     case 5: return zkmi_groth16_load_paged(&j->zk->z, (uint64_t)j->key);
+    case 8: return zkmi_groth16_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     default: {
         /* the round drivers of plonk.prove / fflonk.prove (js/plonk_native.js: proveAsync): the call that makes the host WAIT — the commitments of a
          * round, or the queued work before a read-back — runs here on a pool thread, in the pipeline slot of the proof it belongs to */
@@ -980,6 +981,51 @@ static napi_value js_shm_unlink(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- Groth16 verification (src/groth16_verify.js:26-87; include/zkmi.h zkmi_groth16_vk_load / _verify_batch / _vk_release) ----------------------
+ * groth16VkLoad(curve, alpha1Xyz, beta2Xyz, gamma2Xyz, delta2Xyz, icXyz, nPublic) -> handle: points as (x, y, z) in standard form, little-endian.
+ * groth16VerifyAsync(handle, proofsXyz, publics, nSignals, n) -> Promise<Uint8Array(n)>: verdict bytes (int8: 1 OK, 0 invalid, -1 publics, -2 points);
+ * the batch runs on a libuv pool thread. groth16VkRelease(handle). */
+static napi_value js_groth16_vk_load(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    int32_t curve; double np;
+    pages_t a, b, g, d, ic;
+    if (get_i32(env, argv[0], &curve) || get_pages(env, argv[1], &a) || get_pages(env, argv[2], &b) || get_pages(env, argv[3], &g) || get_pages(env, argv[4], &d) ||
+        get_pages(env, argv[5], &ic) || get_f64(env, argv[6], &np)) BAD_ARG();
+    if (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) BAD_ARG();
+    const size_t n8 = curve == ZKMI_CURVE_BN128 ? 32 : 48;
+    if (np < 0 || np > 1e8 || a.n != 1 || b.n != 1 || g.n != 1 || d.n != 1 || ic.n != 1 || a.len[0] != 3 * n8 || b.len[0] != 6 * n8 || g.len[0] != 6 * n8 ||
+        d.len[0] != 6 * n8 || ic.len[0] != ((size_t)np + 1) * 3 * n8) BAD_ARG();
+    uint64_t h = 0;
+    int rc = ZK_CALL(zkmi_groth16_vk_load(curve, a.ptr[0], b.ptr[0], g.ptr[0], d.ptr[0], ic.ptr[0], (uint32_t)np, &h));
+    if (rc) return throw_zkmi(env, rc);
+    napi_value v;
+    NAPI_OK(napi_create_double(env, (double)h, &v));
+    return v;
+}
+static napi_value js_groth16_verify_async(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    double h, ns, n;
+    pages_t pr, pu;
+    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
+    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
+    uint8_t* out;
+    napi_value res = new_u8(env, (size_t)n, &out);
+    if (!res) BAD_ARG();
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    if (!j) BAD_ARG();
+    j->kind = 8; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
+    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
+    return job_queue(env, j, "zkmi.groth16Verify", argv, 5, res);
+}
+static napi_value js_groth16_vk_release(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    double h;
+    if (get_f64(env, argv[0], &h)) BAD_ARG();
+    int rc = ZK_CALL(zkmi_groth16_vk_release((uint64_t)h));
+    if (rc) return throw_zkmi(env, rc);
+    return NULL;
+}
+
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
@@ -992,6 +1038,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"groth16Finish", js_groth16_finish}, {"joinABCDev", js_join_abc_dev}, {"pointAdd", js_point_add}, {"shmMap", js_shm_map}, {"shmUnlink", js_shm_unlink},
         {"msmTableDev", js_msm_table_dev}, {"msmTableMultiDev", js_msm_table_multi_dev}, {"msmTableMultiDevAsync", js_msm_table_multi_dev_async}, {"msmTableMultiEnqueueDev", js_msm_table_multi_enqueue_dev}, {"msmTableMultiEnqueueMontDev", js_msm_table_multi_enqueue_mont_dev}, {"msmTableMultiCollect", js_msm_table_multi_collect}, {"synchronizeAsync", js_synchronize_async}, {"ipcExport", js_ipc_export}, {"ipcOpen", js_ipc_open}, {"ipcClose", js_ipc_close},
         {"peerCopy", js_peer_copy}, {"peerCopyAsync", js_peer_copy_async}, {"peerFence", js_peer_fence}, {"groth16Reset", js_groth16_reset}, {"groth16KeyCurve", js_groth16_key_curve},
+        {"groth16VkLoad", js_groth16_vk_load}, {"groth16VerifyAsync", js_groth16_verify_async}, {"groth16VkRelease", js_groth16_vk_release},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

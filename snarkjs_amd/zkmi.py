@@ -35,6 +35,7 @@ SYMBOLS = [
     "zkmi_msm_table_multi_enqueue_mont_dev", "zkmi_ntt_padded_dev", "zkmi_fr_batch_multi_dev", "zkmi_plonk_gather_wires_mont_dev", "zkmi_poly_blind_tail_dev", "zkmi_poly_lincomb_dev",
     "zkmi_poly_evaluate_multi_dev", "zkmi_poly_div_by_zerofier_enqueue", "zkmi_plonk_split_t_dev",
     "zkmi_poly_evaluate_dev", "zkmi_poly_is_zero_dev", "zkmi_poly_div_zh_dev", "zkmi_cpoly_interleave_dev", "zkmi_poly_div_by_zerofier_dev", "zkmi_last_kernel_ms",
+    "zkmi_groth16_vk_load", "zkmi_groth16_verify_batch", "zkmi_groth16_vk_release", "zkmi_pairing_dev", "zkmi_groth16_verify_last_ms",
 ]
 
 
@@ -218,6 +219,12 @@ def lib():
     L.zkmi_msm_dev_fallbacks.argtypes = []
     L.zkmi_msm_dev_fallbacks.restype = C.c_ulonglong
     L.zkmi_groth16_coef_layout.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
+    L.zkmi_groth16_vk_load.argtypes = [C.c_int, u8p, u8p, u8p, u8p, u8p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.zkmi_groth16_verify_batch.argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p]
+    L.zkmi_groth16_vk_release.argtypes = [C.c_uint64]
+    L.zkmi_pairing_dev.argtypes = [C.c_int, u8p, u8p, sz, u8p]
+    L.zkmi_groth16_verify_last_ms.argtypes = []
+    L.zkmi_groth16_verify_last_ms.restype = C.c_double
     _lib = _Locked(L)
     return _lib
 
