@@ -244,6 +244,21 @@ int zkmi_groth16_vk_load(int curve, const uint8_t* alpha1_xyz, const uint8_t* be
                          const uint8_t* ic_xyz, uint32_t n_public, uint64_t* vk_handle);
 int zkmi_groth16_verify_batch(uint64_t vk_handle, const uint8_t* proofs_xyz, const uint8_t* publics, uint32_t n_signals, size_t n, int8_t* verdicts);
 int zkmi_groth16_vk_release(uint64_t vk_handle);
+/* plonkVerify (src/plonk_verify.js:29-123) for batches of proofs against one verifying key, on the device, one verdict per proof; same
+ * conventions as the Groth16 trio above (standard form, little-endian, (x, y, z) triples). zkmi_plonk_vk_load: g1_points_xyz = Qm Ql Qr Qo Qc
+ * S1 S2 S3 (3 Fq each), x2_xyz = X_2 (3 Fq2), k1 / k2 32 bytes each; a key point off its curve is refused. zkmi_plonk_verify_batch: proofs = n
+ * records A B C Z T1 T2 T3 Wxi Wxiw (3 Fq each) | eval_a eval_b eval_c eval_s1 eval_s2 eval_zw (32 bytes each, reduced modulo r as
+ * Fr.fromObject does); publics = n x n_signals x 32 bytes. n_signals != nPublic is refused for the whole call with the reference's message
+ * "Invalid number of public inputs" (code -3 of the wrappers). verdicts[i]: 1 valid ("OK!"), 0 pairing check failed ("Invalid Proof"),
+ * -2 a commitment not on the curve ("Proof commitments are not valid."), -1 a public input >= r ("Public inputs are not valid."), checked in
+ * that order; -4 ("Proof evaluations are not valid") is reserved: the reference's test cannot fire. The verifier has a stream, buffers and a
+ * lock of its own: it never touches the pipeline slots of the provers or the Groth16 verifier. */
+int zkmi_plonk_vk_load(int curve, const uint8_t* g1_points_xyz, const uint8_t* x2_xyz, const uint8_t* k1, const uint8_t* k2, uint32_t power, uint32_t n_public,
+                       uint64_t* vk_handle);
+int zkmi_plonk_verify_batch(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, int8_t* verdicts);
+int zkmi_plonk_vk_release(uint64_t vk_handle);
+/* The curve (ZKMI_CURVE_*) and nPublic of a loaded PLONK verifying key, so that a caller can size a batch's buffers: a record is 27 n8q + 192 bytes. */
+int zkmi_plonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public);
 /* Multi-GPU proof (BASELINE configs[2]: MSMs sharded across the GPUs of a node). Every rank loads the shard of the
  * key that holds the witness-side bases of the variables [var_lo, var_hi) (sections 5-8) and the H bases [h_lo, h_hi) (section 9);
  * the section pointers of `zkey` are those of the FULL sections, the library slices them. zkmi_groth16_sums_dev runs the device

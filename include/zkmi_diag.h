@@ -73,6 +73,12 @@ int zkmi_groth16_coef_layout(uint64_t zkey_cache_key, uint64_t* out, int n);
 int zkmi_pairing_dev(int curve, const uint8_t* g1_xyz, const uint8_t* g2_xyz, size_t n, uint8_t* out_f12);
 /* Device time of the verification kernel of the last zkmi_groth16_verify_batch, in milliseconds (HIP events on the verifier's stream); -1: none yet. */
 double zkmi_groth16_verify_last_ms(void);
+/* The intermediate values of the PLONK verifier for ONE proof (inputs as zkmi_plonk_verify_batch with n = 1), so that a wrong verdict can be
+ * located: out = beta gamma alpha xi v1 u L1(xi) PI(xi) r0 (9 x 32 bytes, Fr, standard form) | A1.x A1.y B1.x B1.y (n8q bytes each, affine,
+ * standard form, the point at infinity all-zero): 288 + 4 n8q bytes. All-zero for a proof that fails the input checks. */
+int zkmi_plonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const uint8_t* publics, uint32_t n_signals, uint8_t* out);
+/* Device time of the verification kernel of the last zkmi_plonk_verify_batch, in milliseconds; -1: none yet. */
+double zkmi_plonk_verify_last_ms(void);
 
 #ifdef __cplusplus
 }

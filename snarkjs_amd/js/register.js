@@ -253,11 +253,15 @@ function installFused(snarkjs, options) {
     const pl = (zkey, wtns, logger, o) => (single(o) ? orig.plonk.prove(zkey, wtns, logger, o) : polyProve(plonkN, plonkN.PlonkKey, 11, zkey, wtns));
     const ff = (zkey, wtns, logger, o) => (single(o) ? orig.fflonk.prove(zkey, wtns, logger, o) : polyProve(fflonkN, fflonkN.FflonkKey, 9, zkey, wtns));
     // options.verify: snarkjs.groth16.verify on the device as well (js/groth16_verify_native.js: batches of concurrent calls, keys per vk content)
-    const verifier = options && options.verify ? require("./groth16_verify_native.js").makeVerifier(snarkjs, options) : null;
+    // options.verify as an object picks the protocols: { groth16: true, plonk: true } (verifyPlonk: true is the same as verify.plonk); `verify: true` alone keeps
+    // meaning Groth16 only, and snarkjs.plonk.verify then stays the reference's (js/plonk_verify_native.js otherwise)
+    const vopt = options && options.verify, vobj = vopt && typeof vopt === "object";
+    const verifier = (vobj ? vopt.groth16 : vopt) ? require("./groth16_verify_native.js").makeVerifier(snarkjs, options) : null;
+    const plonkVerifier = (vobj && vopt.plonk) || (options && options.verifyPlonk) ? require("./plonk_verify_native.js").makeVerifier(snarkjs, options) : null;
     snarkjs.groth16 = Object.freeze(Object.assign({}, orig.groth16, { prove: g16, fullProve: fullOf(g16) }, verifier ? { verify: verifier.verify } : {}));
-    snarkjs.plonk = Object.freeze(Object.assign({}, orig.plonk, { prove: pl, fullProve: fullOf(pl) }));
+    snarkjs.plonk = Object.freeze(Object.assign({}, orig.plonk, { prove: pl, fullProve: fullOf(pl) }, plonkVerifier ? { verify: plonkVerifier.verify } : {}));
     snarkjs.fflonk = Object.freeze(Object.assign({}, orig.fflonk, { prove: ff, fullProve: fullOf(ff) }));
-    snarkjs.__zkmiFused = { orig, prover, keys, verifier };
+    snarkjs.__zkmiFused = { orig, prover, keys, verifier, plonkVerifier };
     return snarkjs.__zkmiFused;
 }
 async function uninstallFused(snarkjs) {
@@ -268,6 +272,7 @@ async function uninstallFused(snarkjs) {
     for (const k of st.keys.values()) { try { k.release(); } catch (e) { /* already released */ } }
     st.keys.clear();
     if (st.verifier) st.verifier.release();
+    if (st.plonkVerifier) st.plonkVerifier.release();
     await st.prover.release();
 }
 

@@ -1,0 +1,238 @@
+"""csrc/plonk_verify.cuh on the CPU (tools/plonk_verify_hosttest.hip, the same source with __device__ defined away) against the oracles:
+Keccak-256 against zkmi_keccak256, the six challenges, L1, PI, r0, A1 and B1 against oracle/plonk_verify_oracle.py::verifier_values, and the
+whole per-proof check against tests/plonk_verify_vectors.py::expected_code — whose own composition is checked first (it accepts the golden
+proofs the reference accepted and rejects the tampers). Also the host-only parts of snarkjs_amd.plonk_verify: packing and vk_from_zkey.
+No GPU needed; the new entry points must still refuse to run without one."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import plonk_verify_vectors as V
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOOL = os.path.join(ROOT, "tools", "bin", "plonk_verify_hosttest")
+SRC = os.path.join(ROOT, "tools", "plonk_verify_hosttest.hip")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+CSRC = os.path.join(ROOT, "snarkjs_amd", "csrc")
+_expected = {}
+
+
+def expected(tag, vk, pubs, proof):
+    """expected_code, once per distinct case of this module"""
+    if tag not in _expected:
+        _expected[tag] = V.expected_code(vk, pubs, proof)
+    return _expected[tag]
+
+
+@pytest.fixture(scope="module")
+def tool():
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("plonk_verify.cuh", "pairing.cuh", "pairing_host.hpp", "curve.cuh", "field.cuh", "host_field.hpp")]
+    if not os.path.exists(TOOL) or any(os.path.getmtime(d) > os.path.getmtime(TOOL) for d in deps):
+        os.makedirs(os.path.dirname(TOOL), exist_ok=True)
+        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O0", "-std=c++17", "-I" + CSRC, SRC, "-o", TOOL])
+    p = subprocess.Popen([TOOL], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, bufsize=1)
+
+    def call(*args):
+        p.stdin.write(" ".join(str(a) for a in args) + "\n")
+        p.stdin.flush()
+        out = p.stdout.readline().split()
+        assert out and out[0] != "ERR", out
+        return out
+    yield call
+    p.stdin.close()
+    p.wait()
+
+
+def H(v):
+    return "%x" % int(v)
+
+
+def run(tool, vk, pubs, proof):
+    """(code, dict of the traced values) of the harness for one proof; coordinates reduced modulo q and evaluations given as they fit in 32
+    bytes, as the packing of snarkjs_amd.plonk_verify does"""
+    from snarkjs_amd import zkmi
+    E = V.curve_of(vk)
+    ci = 0 if vk["curve"] == "bn128" else 1
+    w = np.zeros(32, np.uint8)
+    zkmi.check(zkmi.lib().zkmi_fr_root(ci, int(vk["power"]), zkmi.ptr(w)))
+
+    def g1(o):
+        return [H(int(o[0]) % E.P), H(int(o[1]) % E.P), H(int(o[2]) % E.P)]
+    a = ["verify", ci, vk["power"], len(pubs), H(int.from_bytes(w.tobytes(), "little")), H(vk["k1"]), H(vk["k2"])]
+    for k in ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3"):
+        a += g1(vk[k])
+    for c in vk["X_2"]:
+        a += [H(c[0]), H(c[1])]
+    for k in V.POINTS:
+        a += g1(proof[k])
+    a += [H(int(proof[k])) for k in V.EVALS] + [H(x) for x in pubs]
+    out = tool(*a)
+    t = [int(x, 16) for x in out[1:]]
+    val = dict(zip(("beta", "gamma", "alpha", "xi", "v1", "u", "L1", "pi", "r0"), t[:9]))
+    val["A1"] = None if (t[9], t[10]) == (0, 0) else (t[9], t[10])
+    val["B1"] = None if (t[11], t[12]) == (0, 0) else (t[11], t[12])
+    return int(out[0]), val
+
+
+def check_values(got, want):
+    for k in ("beta", "gamma", "alpha", "xi", "u", "pi", "r0", "A1", "B1"):
+        assert got[k] == want[k], k
+    assert got["v1"] == want["v"][1] and got["L1"] == want["L"][1]
+
+
+def test_helper_accepts_goldens_and_rejects_tampers():
+    """the yardstick itself: the composition of the two pinned oracles accepts what the reference accepted and rejects plain tampers"""
+    for f in V.GOLDEN_FILES:
+        vk, pubs, proof = V.golden(f)
+        E = V.curve_of(vk)
+        assert expected(f, vk, pubs, proof) == 1
+        assert V.expected_code(vk, pubs, V.with_(proof, eval_a=str((int(proof["eval_a"]) + 1) % E.R))) == 0
+        assert V.expected_code(vk, pubs, V.with_(proof, eval_a=str(int(proof["eval_a"]) + E.R))) == 1
+        assert V.expected_code(vk, pubs, V.with_(proof, Wxi=V.obj(V.other_point(E, proof, "Wxi")))) == 0
+        for label, pu, p, want in V.tampers(vk, pubs, proof, full=False):
+            if want is not None:
+                assert V.expected_code(vk, pu, p) == want, label
+    vk, pubs, proof = V.golden(V.GOLDEN_FILES[0])
+    E = V.curve_of(vk)
+    assert V.expected_code(vk, pubs, V.with_(proof, A=V.jacobian(E, V.affine(E, proof["A"]), 5))) == 1
+    assert V.expected_code(vk, [str((int(pubs[0]) + 1) % E.R)] + pubs[1:], proof) == 0
+
+
+def test_keccak_matches_library(tool):
+    """the harness hashes through the verifier's own sponge (keccak_lane, and keccak_finish whenever the message ends on an 8-byte lane: 0,
+    136, 272, 1 000); only the ragged tail of 1, 135, 137 — which no transcript has — is padded by the harness itself"""
+    from snarkjs_amd import plonk
+    for n in (0, 1, 135, 136, 137, 272, 1000):
+        msg = bytes((7 * i + n) & 0xff for i in range(n))
+        assert tool("keccak", 0, msg.hex() or "-")[0] == plonk.keccak256(msg).hex(), n
+    assert tool("keccak", 0, "-")[0] == "c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470"
+
+
+@pytest.mark.parametrize("f", V.GOLDEN_FILES)
+def test_values_and_verdict_on_goldens(tool, f):
+    vk, pubs, proof = V.golden(f)
+    code, got = run(tool, vk, pubs, proof)
+    check_values(got, V.values(vk, pubs, proof))
+    assert code == expected(f, vk, pubs, proof) == 1
+
+
+@pytest.mark.parametrize("f", V.GOLDEN_FILES)
+@pytest.mark.parametrize("n", [0, 1, 40])
+def test_values_under_other_public_counts(tool, f, n):
+    vk, _, proof = V.golden(f)
+    v, pu = V.with_n_public(vk, n, 0x70 + n)
+    code, got = run(tool, v, pu, proof)
+    check_values(got, V.values(v, pu, proof))
+    assert code == expected((f, n), v, pu, proof) == 0
+
+
+@pytest.mark.parametrize("f", V.GOLDEN_FILES)
+def test_verify_path_on_tampers(tool, f):
+    vk, pubs, proof = V.golden(f)
+    for label, pu, p, want in V.tampers(vk, pubs, proof, full=(f == V.GOLDEN_FILES[0])):
+        if len(pu) != int(vk["nPublic"]):
+            continue                                  # the signal count is refused before the kernel (tests of the packing and of the device)
+        if want is None:
+            want = expected((f, label), vk, pu, p)
+        code, _ = run(tool, vk, pu, p)
+        assert code == want, label
+
+
+# ---- host-only parts of snarkjs_amd.plonk_verify ------------------------------------------------------------------------------------------
+class _Key:
+    """VerifyingKey without the device call: what pack needs"""
+
+    def __init__(self, vk):
+        from snarkjs_amd import plonk_verify as pv
+        self.curve, self.n8, self.p, self.r = pv._FQ[vk["curve"]]
+        self.n_public = int(vk["nPublic"])
+    record_bytes = property(lambda self: 27 * self.n8 + 192)
+
+
+def test_pack_forms():
+    from snarkjs_amd import plonk_verify as pv
+    for f in (V.GOLDEN_FILES[0], V.GOLDEN_FILES[2]):
+        vk, pubs, proof = V.golden(f)
+        E = V.curve_of(vk)
+        key = _Key(vk)
+        base, pb, n_sig, pre = pv.VerifyingKey.pack(key, [pubs], [proof])
+        assert base.size == key.record_bytes and pb.size == 32 * len(pubs) and n_sig == len(pubs) and pre == [None]
+        n8 = key.n8
+        assert int.from_bytes(base[:n8].tobytes(), "little") == int(proof["A"][0]) and int.from_bytes(base[2 * n8:3 * n8].tobytes(), "little") == 1
+        assert int.from_bytes(base[27 * n8:27 * n8 + 32].tobytes(), "little") == int(proof["eval_a"])
+        as_int = {k: ([int(x) for x in v] if isinstance(v, list) else int(v) if k.startswith("eval") else v) for k, v in proof.items()}
+        as_hex = {k: ([hex(int(x)) for x in v] if isinstance(v, list) else hex(int(v)) if k.startswith("eval") else v) for k, v in proof.items()}
+        for alt, pu in ((as_int, [int(x) for x in pubs]), (as_hex, [hex(int(x)) for x in pubs])):
+            r2, p2, _, _ = pv.VerifyingKey.pack(key, [pu], [alt])
+            assert np.array_equal(r2, base) and np.array_equal(p2, pb)
+        jac = V.with_(proof, B=V.jacobian(E, V.affine(E, proof["B"]), 9), C=["0", "1", "0"], eval_b=str(int(proof["eval_b"]) + E.R * (1 << 20)))
+        r3, _, _, _ = pv.VerifyingKey.pack(key, [pubs], [jac])
+        assert int.from_bytes(r3[5 * n8:6 * n8].tobytes(), "little") == 9 and not r3[6 * n8:7 * n8].any() and not r3[8 * n8:9 * n8].any()
+        assert int.from_bytes(r3[27 * n8 + 32:27 * n8 + 64].tobytes(), "little") == int(proof["eval_b"])          # does not fit 32 bytes: reduced
+        _, _, _, pre = pv.VerifyingKey.pack(key, [[str(E.R)] + pubs[1:], pubs, [str(-1)] + pubs[1:]], [proof] * 3)
+        assert pre == [-1, None, -1]
+        _, p4, n_sig, _ = pv.VerifyingKey.pack(key, [pubs + ["1"]], [proof])
+        assert n_sig == len(pubs) + 1 and p4.size == 32 * n_sig
+        with pytest.raises(ValueError):
+            pv.VerifyingKey.pack(key, [pubs, pubs[:-1]], [proof, proof])
+        assert pv.VerifyingKey._on_curve(key, proof["A"]) and pv.VerifyingKey._on_curve(key, jac["B"]) and pv.VerifyingKey._on_curve(key, ["0", "1", "0"])
+        assert not pv.VerifyingKey._on_curve(key, [str(int(proof["A"][0]) + 1), proof["A"][1], "1"])
+
+
+@pytest.mark.parametrize("tag", ["plonk_bn128_small", "plonk_bn128_n2048", "plonk_bls12381_small"])
+def test_vk_from_zkey_equals_golden(tag, golden_dir):
+    from snarkjs_amd import plonk_verify as pv
+    import json
+    want = json.load(open(os.path.join(golden_dir, tag + ".json")))["vk"]
+    got = pv.vk_from_zkey(open(os.path.join(golden_dir, tag + ".zkey"), "rb").read())
+    assert set(got) == set(want)
+    for k in want:
+        assert got[k] == want[k], k
+
+
+def test_rejects_other_keys():
+    from snarkjs_amd import plonk_verify as pv
+    vk, _, _ = V.golden(V.GOLDEN_FILES[0])
+    with pytest.raises(ValueError, match="PLONK"):
+        pv.VerifyingKey(dict(vk, protocol="groth16"))
+    with pytest.raises(ValueError, match="curve"):
+        pv.VerifyingKey(dict(vk, curve="bw6"))
+
+
+def test_new_entry_points_fail_without_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a device is present")
+    from snarkjs_amd import zkmi, plonk_verify
+    L = zkmi.lib()
+    for s in ("zkmi_plonk_vk_load", "zkmi_plonk_verify_batch", "zkmi_plonk_vk_release", "zkmi_plonk_verify_trace_dev"):
+        assert hasattr(L, s) and s in zkmi.SYMBOLS
+    vk, pubs, proof = V.golden(V.GOLDEN_FILES[0])
+    with pytest.raises(zkmi.ZkmiError, match="no HIP device"):
+        plonk_verify.VerifyingKey(vk)
+    with pytest.raises(zkmi.ZkmiError, match="no HIP device"):
+        plonk_verify.verify(vk, pubs, proof)
+    out = np.zeros(2048, np.uint8)
+    assert L.zkmi_plonk_verify_batch(1, zkmi.ptr(out), zkmi.ptr(out), 2, 1, zkmi.ptr(out)) != 0
+    assert b"no HIP device" in L.zkmi_last_error()
+
+
+def test_addon_plonk_entries_fail_without_device():
+    node = shutil.which("node")
+    addon = os.path.join(ROOT, "snarkjs_amd", "napi", "zkmi_napi.node")
+    if node is None or not os.path.exists(addon):
+        pytest.skip("node or the built addon is missing")
+    js = ("const a=require(%r);for(const k of ['plonkVkLoad','plonkVerifyAsync','plonkVkRelease']) if(typeof a[k]!=='function'){console.log('missing',k);process.exit(3)}"
+          "if(a.deviceCount()!==0){console.log('ok device');process.exit(0)}"
+          "const z=(n)=>new Uint8Array(n);try{a.plonkVkLoad(0,z(768),z(192),z(32),z(32),3,2);console.log('no throw');process.exit(4)}"
+          "catch(e){if(!/no HIP device/.test(e.message)){console.log(e.message);process.exit(5)}}"
+          "const {VerifyingKey}=require(%r);const vk=require(%r).vk;try{new VerifyingKey(vk);console.log('no throw js');process.exit(6)}"
+          "catch(e){if(!/no HIP device/.test(e.message)){console.log(e.message);process.exit(7)}}console.log('ok')") % (
+        addon, os.path.join(ROOT, "snarkjs_amd", "js", "plonk_verify_native.js"), os.path.join(ROOT, "tests", "golden", "plonk_bn128_small.json"))
+    r = subprocess.run([node, "-e", js], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr

@@ -1,7 +1,9 @@
 """Batch Groth16 verification rate on one GPU: verifications/s through VerifyingKey.verify_many (from the JSON objects) and through
 verify_raw (packed arrays, no parsing) for BN254 and BLS12-381 at several batch sizes, the verification kernel's device time per proof (HIP
 events: zkmi_groth16_verify_last_ms), and, in the same run and outside the timed windows, the reference's own single-thread WASM verify rate
-on this host (tools/ref_wasm_verify.js through the bundle in oracle/_ref/). Warm-up first, then `reps` timed windows per point; the JSON line
+on this host (tools/ref_wasm_verify.js through the bundle in oracle/_ref/). --protocol plonk does the same for PLONK (snarkjs_amd.plonk_verify, sizes 1 /
+64 / 4 096, batches of DISTINCT device proofs: see main_plonk) next to the reference's WASM plonk.verify, and measures the Groth16 verify rate at batch 4 096 in the same run: the PLONK rate is expected
+not to fall below half of it (`plonk_vs_groth16_4096`). Warm-up first, then `reps` timed windows per point; the JSON line
 reports the median and the spread. The batches hold the golden proof in distinct encodings (Jacobian z = 2 + i for entry i), so every lane
 decodes different bytes; the publics, and so the vk_x double-and-add, are the same in every lane. Prints one JSON line."""
 import json
@@ -26,12 +28,12 @@ def rate(fn, n, reps):
     return {"per_s": round(n / statistics.median(ts), 1), "min_s": round(min(ts), 5), "max_s": round(max(ts), 5)}
 
 
-def wasm_baseline(count):
+def wasm_baseline(count, protocol="groth16"):
     node = shutil.which("node")
     script = os.path.join(ROOT, "tools", "ref_wasm_verify.js")
     if node is None or not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "build", "snarkjs.min.js")):
         return None
-    r = subprocess.run([node, "--harmony-optional-chaining", "--harmony-nullish", script, str(count)], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([node, "--harmony-optional-chaining", "--harmony-nullish", script, str(count)] + ([protocol] if protocol != "groth16" else []), capture_output=True, text=True, timeout=900)
     return json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 else {"error": r.stderr[-500:]}
 
 
@@ -72,5 +74,63 @@ def main():
     print(json.dumps(out))
 
 
+def main_plonk():
+    """Headline batches hold DISTINCT valid proofs: `VERIFYBENCH_DISTINCT` (256) device proofs of the golden witness, each with fresh blinding, so
+    that the lanes of a wavefront carry different challenges and different Straus scalars (entry i is proof i mod 256: any 64 consecutive lanes
+    differ) and the additions of B1 cost what they cost in use. `uniform_4096` is the same measurement on one proof in distinct encodings, where all
+    lanes of a wavefront agree on every scalar bit: the divergence-free best case, kept beside it."""
+    import plonk_verify_vectors as PV
+    import verify_vectors as V
+    import groth16_verify_oracle as O
+    from snarkjs_amd import groth16_verify, plonk, plonk_verify, zkmi
+    sizes = [int(x) for x in os.environ.get("VERIFYBENCH_SIZES", "1,64,4096").split(",")]
+    reps = int(os.environ.get("VERIFYBENCH_REPS", "3"))
+    n_distinct = max(64, int(os.environ.get("VERIFYBENCH_DISTINCT", "256")))
+    out = {"what": "plonk batch verify", "reps": reps, "distinct_proofs": n_distinct,
+           "wasm_single_thread": wasm_baseline(int(os.environ.get("VERIFYBENCH_WASM_COUNT", "40")), "plonk"), "curves": {}}
+    gd = os.path.join(ROOT, "tests", "golden")
+    for tag, g16 in (("plonk_bn128_n2048", "groth16_bn128_n1024.json"), ("plonk_bls12381_small", "groth16_bls12381_n1024.json")):
+        vk, pubs, proof = PV.golden(tag + ".json")
+        E = PV.curve_of(vk)
+        pkey = plonk.PlonkKey(open(os.path.join(gd, tag + ".zkey"), "rb").read())
+        wtns = open(os.path.join(gd, tag + ".wtns"), "rb").read()
+        distinct = [plonk.prove(pkey, wtns)["proof"] for _ in range(n_distinct)]
+        pkey.release()
+        assert len({p["Wxi"][0] for p in distinct}) == n_distinct
+        key = plonk_verify.VerifyingKey(vk)
+
+        def point(proofs, n):
+            lists = [pubs] * n
+            recs, pu, ns, _ = key.pack(lists, proofs)
+            entry = {"verify_many": rate(lambda: key.verify_many(lists, proofs), n, reps), "verify_raw": rate(lambda: key.verify_raw(recs, pu, ns, n), n, reps)}
+            kms = zkmi.lib().zkmi_plonk_verify_last_ms()
+            entry["kernel_ms"] = round(kms, 3)
+            entry["kernel_us_per_proof"] = round(1000.0 * kms / n, 3)
+            assert all(c == 1 for c in key.verify_raw(recs, pu, ns, n))
+            return entry
+        res = {str(n): point([distinct[i % n_distinct] for i in range(n)], n) for n in sizes}
+        # one proof 4 096 times, one commitment per entry in a distinct Jacobian encoding (z = 2 + i): every lane of a wavefront takes the same branches
+        res["uniform_4096"] = point([PV.with_(proof, **{PV.POINTS[i % 9]: PV.jacobian(E, PV.affine(E, proof[PV.POINTS[i % 9]]), 2 + i)}) for i in range(4096)], 4096)
+        key.release()
+        # the same device's Groth16 verify rate at batch 4 096, same run
+        gvk, gpubs, gproof = V.golden(g16)
+        GE = O.BN254 if gvk["curve"] == "bn128" else O.BLS12381
+        gkey = groth16_verify.VerifyingKey(gvk)
+        gproofs = [V.jacobian(GE, gproof, 2 + i, 3 + i) for i in range(4096)]
+        grecs, gpu, gns, _ = gkey.pack([gpubs] * 4096, gproofs)
+        res["groth16_4096"] = {"verify_many": rate(lambda: gkey.verify_many([gpubs] * 4096, gproofs), 4096, reps), "verify_raw": rate(lambda: gkey.verify_raw(grecs, gpu, gns, 4096), 4096, reps)}
+        gkey.release()
+        if "4096" in res:
+            res["plonk_vs_groth16_4096"] = {k: round(res["4096"][k]["per_s"] / res["groth16_4096"][k]["per_s"], 3) for k in ("verify_many", "verify_raw")}
+        wasm = (out["wasm_single_thread"] or {}).get(vk["curve"])
+        if wasm and "4096" in res:
+            res["ratio_verify_many_4096_vs_wasm"] = round(res["4096"]["verify_many"]["per_s"] / wasm["per_s"], 1)
+        out["curves"][vk["curve"]] = res
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    main()
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--protocol", choices=["groth16", "plonk"], default="groth16")
+    main_plonk() if ap.parse_args().protocol == "plonk" else main()
