@@ -259,6 +259,22 @@ int zkmi_plonk_verify_batch(uint64_t vk_handle, const uint8_t* proofs, const uin
 int zkmi_plonk_vk_release(uint64_t vk_handle);
 /* The curve (ZKMI_CURVE_*) and nPublic of a loaded PLONK verifying key, so that a caller can size a batch's buffers: a record is 27 n8q + 192 bytes. */
 int zkmi_plonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public);
+/* fflonkVerify (src/fflonk_verify.js:28-137) for batches of proofs against one verifying key, on the device, one verdict per proof; same
+ * conventions as the PLONK calls above. BN254 only: ZKMI_CURVE_BLS12381 is refused (the reference has no FFLONK on that curve). zkmi_fflonk_vk_load:
+ * c0_xyz = C0 (3 Fq), x2_xyz = X_2 (3 Fq2), consts = k1 k2 w3 w4 w8 wr (32 bytes each, standard form); w is Fr.w[power]. An X_2 off its curve
+ * is refused; a C0 off the curve loads, and every proof under that key gets -2, as the reference has it. zkmi_fflonk_verify_batch: proofs = n
+ * records C1 C2 W1 W2 (3 Fq each) | ql qr qm qo qc s1 s2 s3 a b c z zw t1w t2w (32 bytes each, reduced modulo r as Fr.fromObject does; the
+ * proof's `inv` is not read): 12 n8q + 480 bytes; publics = n x n_signals x 32 bytes. The reference tests the number of signals FIRST:
+ * n_signals != nPublic is refused for the whole call with its message "Number of public signals does not match with vk" (code -3 of the
+ * wrappers, for every proof of the call whatever its commitments are). verdicts[i]: -2 a commitment (or C0) not on the curve ("Proof commitments are not valid"), -1 a
+ * public input >= r ("Public inputs are not valid."), checked in that order, then 0 pairing check failed ("Invalid Proof") or 1 valid
+ * ("PROOF VERIFIED SUCCESSFULLY"); -4 ("Proof evaluations are not valid.") is reserved: the reference's test cannot fire. The verifier has a
+ * stream, buffers and a lock of its own: it never touches the pipeline slots of the provers or the other verifiers. */
+int zkmi_fflonk_vk_load(int curve, const uint8_t* c0_xyz, const uint8_t* x2_xyz, const uint8_t* consts, uint32_t power, uint32_t n_public, uint64_t* vk_handle);
+int zkmi_fflonk_verify_batch(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, int8_t* verdicts);
+int zkmi_fflonk_vk_release(uint64_t vk_handle);
+/* The curve (ZKMI_CURVE_*) and nPublic of a loaded FFLONK verifying key, so that a caller can size a batch's buffers. */
+int zkmi_fflonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public);
 /* Multi-GPU proof (BASELINE configs[2]: MSMs sharded across the GPUs of a node). Every rank loads the shard of the
  * key that holds the witness-side bases of the variables [var_lo, var_hi) (sections 5-8) and the H bases [h_lo, h_hi) (section 9);
  * the section pointers of `zkey` are those of the FULL sections, the library slices them. zkmi_groth16_sums_dev runs the device

@@ -79,6 +79,12 @@ double zkmi_groth16_verify_last_ms(void);
 int zkmi_plonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const uint8_t* publics, uint32_t n_signals, uint8_t* out);
 /* Device time of the verification kernel of the last zkmi_plonk_verify_batch, in milliseconds; -1: none yet. */
 double zkmi_plonk_verify_last_ms(void);
+/* The intermediate values of the FFLONK verifier for ONE proof (inputs as zkmi_fflonk_verify_batch with n = 1): out = beta gamma xi alpha y r0
+ * r1 r2 (8 x 32 bytes, Fr, standard form) | A1.x A1.y B1.x B1.y (n8q bytes each, affine, standard form, the point at infinity all-zero; B1 is
+ * W2): 256 + 4 n8q bytes. All-zero for a proof that fails the input checks. */
+int zkmi_fflonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const uint8_t* publics, uint32_t n_signals, uint8_t* out);
+/* Device time of the verification kernel of the last zkmi_fflonk_verify_batch, in milliseconds; -1: none yet. */
+double zkmi_fflonk_verify_last_ms(void);
 
 #ifdef __cplusplus
 }

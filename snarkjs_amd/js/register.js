@@ -254,14 +254,16 @@ function installFused(snarkjs, options) {
     const ff = (zkey, wtns, logger, o) => (single(o) ? orig.fflonk.prove(zkey, wtns, logger, o) : polyProve(fflonkN, fflonkN.FflonkKey, 9, zkey, wtns));
     // options.verify: snarkjs.groth16.verify on the device as well (js/groth16_verify_native.js: batches of concurrent calls, keys per vk content)
     // options.verify as an object picks the protocols: { groth16: true, plonk: true } (verifyPlonk: true is the same as verify.plonk); `verify: true` alone keeps
-    // meaning Groth16 only, and snarkjs.plonk.verify then stays the reference's (js/plonk_verify_native.js otherwise)
+    // meaning Groth16 only, and snarkjs.plonk.verify then stays the reference's (js/plonk_verify_native.js otherwise). { fflonk: true } (alias verifyFflonk: true) does
+    // the same for snarkjs.fflonk.verify (js/fflonk_verify_native.js, BN254 only)
     const vopt = options && options.verify, vobj = vopt && typeof vopt === "object";
     const verifier = (vobj ? vopt.groth16 : vopt) ? require("./groth16_verify_native.js").makeVerifier(snarkjs, options) : null;
     const plonkVerifier = (vobj && vopt.plonk) || (options && options.verifyPlonk) ? require("./plonk_verify_native.js").makeVerifier(snarkjs, options) : null;
+    const fflonkVerifier = (vobj && vopt.fflonk) || (options && options.verifyFflonk) ? require("./fflonk_verify_native.js").makeVerifier(snarkjs, options) : null;
     snarkjs.groth16 = Object.freeze(Object.assign({}, orig.groth16, { prove: g16, fullProve: fullOf(g16) }, verifier ? { verify: verifier.verify } : {}));
     snarkjs.plonk = Object.freeze(Object.assign({}, orig.plonk, { prove: pl, fullProve: fullOf(pl) }, plonkVerifier ? { verify: plonkVerifier.verify } : {}));
-    snarkjs.fflonk = Object.freeze(Object.assign({}, orig.fflonk, { prove: ff, fullProve: fullOf(ff) }));
-    snarkjs.__zkmiFused = { orig, prover, keys, verifier, plonkVerifier };
+    snarkjs.fflonk = Object.freeze(Object.assign({}, orig.fflonk, { prove: ff, fullProve: fullOf(ff) }, fflonkVerifier ? { verify: fflonkVerifier.verify } : {}));
+    snarkjs.__zkmiFused = { orig, prover, keys, verifier, plonkVerifier, fflonkVerifier };
     return snarkjs.__zkmiFused;
 }
 async function uninstallFused(snarkjs) {
@@ -273,6 +275,7 @@ async function uninstallFused(snarkjs) {
     st.keys.clear();
     if (st.verifier) st.verifier.release();
     if (st.plonkVerifier) st.plonkVerifier.release();
+    if (st.fflonkVerifier) st.fflonkVerifier.release();
     await st.prover.release();
 }
 

@@ -155,6 +155,7 @@ static int job_run(job_t* j) {
     case 5: return zkmi_groth16_load_paged(&j->zk->z, (uint64_t)j->key);
     case 8: return zkmi_groth16_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 9: return zkmi_plonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
+    case 10: return zkmi_fflonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     default: {
         /* the round drivers of plonk.prove / fflonk.prove (js/plonk_native.js: proveAsync): the call that makes the host WAIT — the commitments of a
          * round, or the queued work before a read-back — runs here on a pool thread, in the pipeline slot of the proof it belongs to */
@@ -1076,6 +1077,70 @@ static napi_value js_plonk_vk_release(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- FFLONK verification (src/fflonk_verify.js:28-137; include/zkmi.h zkmi_fflonk_vk_load / _verify_batch / _vk_info / _vk_release), BN254 only ---
+ * fflonkVkLoad(curve, c0Xyz, x2Xyz, consts (k1 k2 w3 w4 w8 wr), power, nPublic) -> handle.
+ * fflonkVerifyAsync(handle, proofs, publics, nSignals, n) -> Promise<Uint8Array(n)>: verdict bytes (int8: 1 valid, 0 invalid, -1 publics, -2 points); a
+ * signal count other than the key's nPublic rejects with "Number of public signals does not match with vk". The batch runs on a libuv pool thread.
+ * fflonkVkInfo(handle) -> { curve, nPublic }. fflonkVkRelease(handle). */
+static napi_value js_fflonk_vk_load(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    int32_t curve; double power, np;
+    pages_t c0, x, k;
+    if (get_i32(env, argv[0], &curve) || get_pages(env, argv[1], &c0) || get_pages(env, argv[2], &x) || get_pages(env, argv[3], &k) ||
+        get_f64(env, argv[4], &power) || get_f64(env, argv[5], &np)) BAD_ARG();
+    if (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) BAD_ARG();
+    const size_t n8 = curve == ZKMI_CURVE_BN128 ? 32 : 48;
+    if (np < 0 || np > 1e8 || power < 0 || power > 32 || c0.n != 1 || x.n != 1 || k.n != 1 || c0.len[0] != 3 * n8 || x.len[0] != 6 * n8 || k.len[0] != 192) BAD_ARG();
+    uint64_t h = 0;
+    int rc = ZK_CALL(zkmi_fflonk_vk_load(curve, c0.ptr[0], x.ptr[0], k.ptr[0], (uint32_t)power, (uint32_t)np, &h));          /* refuses BLS12-381 */
+    if (rc) return throw_zkmi(env, rc);
+    napi_value v;
+    NAPI_OK(napi_create_double(env, (double)h, &v));
+    return v;
+}
+static napi_value js_fflonk_verify_async(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    double h, ns, n;
+    pages_t pr, pu;
+    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
+    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
+    int curve = 0; uint32_t np = 0;                       /* the record buffer must have the size of the handle's own curve */
+    int rc = ZK_CALL(zkmi_fflonk_vk_info((uint64_t)h, &curve, &np));
+    if (rc) return throw_zkmi(env, rc);
+    if (pr.len[0] != (size_t)n * (12 * (curve == ZKMI_CURVE_BN128 ? 32 : 48) + 480)) BAD_ARG();
+    uint8_t* out;
+    napi_value res = new_u8(env, (size_t)n, &out);
+    if (!res) BAD_ARG();
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    if (!j) BAD_ARG();
+    j->kind = 10; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
+    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
+    return job_queue(env, j, "zkmi.fflonkVerify", argv, 5, res);
+}
+static napi_value js_fflonk_vk_info(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    double h;
+    if (get_f64(env, argv[0], &h)) BAD_ARG();
+    int curve = 0; uint32_t np = 0;
+    int rc = ZK_CALL(zkmi_fflonk_vk_info((uint64_t)h, &curve, &np));
+    if (rc) return throw_zkmi(env, rc);
+    napi_value o, c, p;
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_double(env, (double)curve, &c));
+    NAPI_OK(napi_create_double(env, (double)np, &p));
+    NAPI_OK(napi_set_named_property(env, o, "curve", c));
+    NAPI_OK(napi_set_named_property(env, o, "nPublic", p));
+    return o;
+}
+static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    double h;
+    if (get_f64(env, argv[0], &h)) BAD_ARG();
+    int rc = ZK_CALL(zkmi_fflonk_vk_release((uint64_t)h));
+    if (rc) return throw_zkmi(env, rc);
+    return NULL;
+}
+
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
@@ -1090,6 +1155,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"peerCopy", js_peer_copy}, {"peerCopyAsync", js_peer_copy_async}, {"peerFence", js_peer_fence}, {"groth16Reset", js_groth16_reset}, {"groth16KeyCurve", js_groth16_key_curve},
         {"groth16VkLoad", js_groth16_vk_load}, {"groth16VerifyAsync", js_groth16_verify_async}, {"groth16VkRelease", js_groth16_vk_release},
         {"plonkVkLoad", js_plonk_vk_load}, {"plonkVerifyAsync", js_plonk_verify_async}, {"plonkVkRelease", js_plonk_vk_release},
+        {"fflonkVkLoad", js_fflonk_vk_load}, {"fflonkVerifyAsync", js_fflonk_verify_async}, {"fflonkVkInfo", js_fflonk_vk_info}, {"fflonkVkRelease", js_fflonk_vk_release},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -37,6 +37,7 @@ SYMBOLS = [
     "zkmi_poly_evaluate_dev", "zkmi_poly_is_zero_dev", "zkmi_poly_div_zh_dev", "zkmi_cpoly_interleave_dev", "zkmi_poly_div_by_zerofier_dev", "zkmi_last_kernel_ms",
     "zkmi_groth16_vk_load", "zkmi_groth16_verify_batch", "zkmi_groth16_vk_release", "zkmi_pairing_dev", "zkmi_groth16_verify_last_ms",
     "zkmi_plonk_vk_load", "zkmi_plonk_verify_batch", "zkmi_plonk_vk_release", "zkmi_plonk_vk_info", "zkmi_plonk_verify_trace_dev", "zkmi_plonk_verify_last_ms",
+    "zkmi_fflonk_vk_load", "zkmi_fflonk_verify_batch", "zkmi_fflonk_vk_release", "zkmi_fflonk_vk_info", "zkmi_fflonk_verify_trace_dev", "zkmi_fflonk_verify_last_ms",
 ]
 
 
@@ -233,6 +234,13 @@ def lib():
     L.zkmi_plonk_verify_trace_dev.argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, u8p]
     L.zkmi_plonk_verify_last_ms.argtypes = []
     L.zkmi_plonk_verify_last_ms.restype = C.c_double
+    L.zkmi_fflonk_vk_load.argtypes = [C.c_int, u8p, u8p, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.zkmi_fflonk_verify_batch.argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p]
+    L.zkmi_fflonk_vk_release.argtypes = [C.c_uint64]
+    L.zkmi_fflonk_vk_info.argtypes = [C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
+    L.zkmi_fflonk_verify_trace_dev.argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, u8p]
+    L.zkmi_fflonk_verify_last_ms.argtypes = []
+    L.zkmi_fflonk_verify_last_ms.restype = C.c_double
     _lib = _Locked(L)
     return _lib
 

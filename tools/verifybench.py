@@ -4,7 +4,8 @@ events: zkmi_groth16_verify_last_ms), and, in the same run and outside the timed
 on this host (tools/ref_wasm_verify.js through the bundle in oracle/_ref/). --protocol plonk does the same for PLONK (snarkjs_amd.plonk_verify, sizes 1 /
 64 / 4 096, batches of DISTINCT device proofs: see main_plonk) next to the reference's WASM plonk.verify, and measures the Groth16 verify rate at batch 4 096 in the same run: the PLONK rate is expected
 not to fall below half of it (`plonk_vs_groth16_4096`). Warm-up first, then `reps` timed windows per point; the JSON line
-reports the median and the spread. The batches hold the golden proof in distinct encodings (Jacobian z = 2 + i for entry i), so every lane
+reports the median and the spread. --protocol fflonk (BN254; snarkjs_amd.fflonk_verify, main_fflonk) reports the FFLONK rate on batches of distinct device
+proofs next to three yardsticks of the same run: the reference's WASM fflonk.verify, and this library's PLONK and Groth16 verify rates at batch 4 096. The batches hold the golden proof in distinct encodings (Jacobian z = 2 + i for entry i), so every lane
 decodes different bytes; the publics, and so the vk_x double-and-add, are the same in every lane. Prints one JSON line."""
 import json
 import os
@@ -129,8 +130,70 @@ def main_plonk():
     print(json.dumps(out))
 
 
+def main_fflonk():
+    """As main_plonk, for FFLONK on BN254: `VERIFYBENCH_DISTINCT` (256) device proofs of the golden witness with fresh blinding each, tiled to the batch size;
+    `uniform_4096` is one proof repeated (one commitment per entry in a distinct Jacobian encoding): no divergence in the Straus sum; size 1 is the
+    latency of one proof alone. In the same run: PLONK on 256 distinct device proofs tiled to 4 096 and Groth16 at 4 096 (the golden proof in distinct
+    encodings), and `fflonk_vs_plonk_4096` / `fflonk_vs_groth16_4096`."""
+    import fflonk_verify_vectors as FV
+    import plonk_verify_vectors as PV
+    import verify_vectors as V
+    import groth16_verify_oracle as O
+    from snarkjs_amd import fflonk, fflonk_verify, groth16_verify, plonk, plonk_verify, zkmi
+    sizes = [int(x) for x in os.environ.get("VERIFYBENCH_SIZES", "1,64,4096").split(",")]
+    reps = int(os.environ.get("VERIFYBENCH_REPS", "5"))
+    n_distinct = max(64, int(os.environ.get("VERIFYBENCH_DISTINCT", "256")))
+    out = {"what": "fflonk batch verify", "reps": reps, "distinct_proofs": n_distinct,
+           "wasm_single_thread": wasm_baseline(int(os.environ.get("VERIFYBENCH_WASM_COUNT", "40")), "fflonk"), "curves": {}}
+    gd = os.path.join(ROOT, "tests", "golden")
+    L = zkmi.lib()
+
+    def point(key, last_ms, lists, proofs):
+        n = len(proofs)
+        recs, pu, ns, _ = key.pack(lists, proofs)
+        entry = {"verify_many": rate(lambda: key.verify_many(lists, proofs), n, reps), "verify_raw": rate(lambda: key.verify_raw(recs, pu, ns, n), n, reps)}
+        kms = last_ms()
+        entry["kernel_ms"] = round(kms, 3)
+        entry["kernel_us_per_proof"] = round(1000.0 * kms / n, 3)
+        assert all(c == 1 for c in key.verify_raw(recs, pu, ns, n))
+        return entry
+    tag = "fflonk_bn128_n256"
+    vk, pubs, proof = FV.golden(tag + ".json")
+    res_all = fflonk.prove_many(open(os.path.join(gd, tag + ".zkey"), "rb").read(), [open(os.path.join(gd, tag + ".wtns"), "rb").read()] * n_distinct)
+    distinct = [r["proof"] for r in res_all]
+    assert len({p["polynomials"]["W2"][0] for p in distinct}) == n_distinct
+    key = fflonk_verify.VerifyingKey(vk)
+    res = {str(n): point(key, L.zkmi_fflonk_verify_last_ms, [pubs] * n, [distinct[i % n_distinct] for i in range(n)]) for n in sizes}
+    res["uniform_4096"] = point(key, L.zkmi_fflonk_verify_last_ms, [pubs] * 4096,
+                                [FV.with_point(proof, FV.POINTS[i % 4], FV.jacobian(FV.affine(proof["polynomials"][FV.POINTS[i % 4]]), 2 + i)) for i in range(4096)])
+    key.release()
+    # yardstick: PLONK on distinct device proofs, batch 4 096, same run
+    ptag = "plonk_bn128_n2048"
+    pvk, ppubs, _ = PV.golden(ptag + ".json")
+    pkey = plonk.PlonkKey(open(os.path.join(gd, ptag + ".zkey"), "rb").read())
+    pw = open(os.path.join(gd, ptag + ".wtns"), "rb").read()
+    pdistinct = [plonk.prove(pkey, pw)["proof"] for _ in range(n_distinct)]
+    pkey.release()
+    vkey = plonk_verify.VerifyingKey(pvk)
+    res["plonk_4096"] = point(vkey, L.zkmi_plonk_verify_last_ms, [ppubs] * 4096, [pdistinct[i % n_distinct] for i in range(4096)])
+    vkey.release()
+    # yardstick: Groth16, batch 4 096, same run
+    gvk, gpubs, gproof = V.golden("groth16_bn128_n1024.json")
+    gkey = groth16_verify.VerifyingKey(gvk)
+    res["groth16_4096"] = point(gkey, L.zkmi_groth16_verify_last_ms, [gpubs] * 4096, [V.jacobian(O.BN254, gproof, 2 + i, 3 + i) for i in range(4096)])
+    gkey.release()
+    if "4096" in res:
+        for other in ("plonk", "groth16"):
+            res[f"fflonk_vs_{other}_4096"] = {k: round(res["4096"][k]["per_s"] / res[other + "_4096"][k]["per_s"], 3) for k in ("verify_many", "verify_raw")}
+        wasm = (out["wasm_single_thread"] or {}).get("bn128")
+        if wasm:
+            res["ratio_verify_many_4096_vs_wasm"] = round(res["4096"]["verify_many"]["per_s"] / wasm["per_s"], 1)
+    out["curves"]["bn128"] = res
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument("--protocol", choices=["groth16", "plonk"], default="groth16")
-    main_plonk() if ap.parse_args().protocol == "plonk" else main()
+    ap.add_argument("--protocol", choices=["groth16", "plonk", "fflonk"], default="groth16")
+    {"groth16": main, "plonk": main_plonk, "fflonk": main_fflonk}[ap.parse_args().protocol]()
