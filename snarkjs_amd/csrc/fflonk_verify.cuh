@@ -3,7 +3,7 @@
 // One proof per lane. The number of public signals is a property of the call and is tested by the caller first, as the reference tests it first
 // (-3); a lane then tests, in the reference's order: C1 C2 W1 W2 decoded as G1.fromObject does and, with the key's C0, checked on the curve (-2),
 // the public signals below r (-1), and the pairing (0 / 1). Values exactly as oracle/fflonk_verify_oracle.py::verifier_values states them:
-// the five challenges beta gamma xiSeed alpha y by Keccak-256 (plonk_verify.cuh's sponge; the transcript's encoding is PLONK's), the roots
+// the five challenges beta gamma xiSeed alpha y by Keccak-256 (kzg_verify.cuh's sponge; the transcript's encoding is PLONK's), the roots
 // S0 = h0 w8^i, S1 = h1 w4^i, S2 = h2 w3^i, S2' = h2 wr w3^i with h0 = xiSeed^3, h1 = xiSeed^6, h2 = xiSeed^8, xi = xiSeed^24, then Z_H, L_i, PI,
 // r0 r1 r2, mulH0 mulH1 mulH2, the quotients q1 = alpha mulH0 / mulH1, q2 = alpha^2 mulH0 / mulH2, e = r0 + q1 r1 + q2 r2 and
 //     A1 = C0 + q1 C1 + q2 C2 - e G - mulH0 W1 + y W2,        e(-A1, [1]_2) e(W2, X_2) == 1.
@@ -23,7 +23,7 @@
 //
 // Like plonk_verify.cuh this is __device__ code that also compiles for the host (tools/fflonk_verify_hosttest.hip, __device__ defined away).
 #pragma once
-#include "plonk_verify.cuh"
+#include "kzg_verify.cuh"
 
 namespace zkmi {
 
@@ -68,45 +68,21 @@ template <class C> ZK_PAIR_OP void fflonk_vk_prepare(const uint32_t* c0_xyz, con
     vk->c0[1] = P.y;
     const Fp<C> sx = fp_from_mont(P.x), sy = fp_from_mont(P.y);
     for (int i = 0; i < N; i++) { vk->c0_std[i] = sx.l[i]; vk->c0_std[N + i] = sy.l[i]; }
-    Fp<C> gx, gy;
-    Affine<Fp2<C>> G;
-    for (int i = 0; i < N; i++) {
-        gx.l[i] = PlonkGen<C>::g1(i); gy.l[i] = PlonkGen<C>::g1(N + i);
-        G.x.c0.l[i] = PlonkGen<C>::g2(i); G.x.c1.l[i] = PlonkGen<C>::g2(N + i);
-        G.y.c0.l[i] = PlonkGen<C>::g2(2 * N + i); G.y.c1.l[i] = PlonkGen<C>::g2(3 * N + i);
+    vk->bad = kzg_vk_prepare(x2_xyz, omega_mont, power, K, vk->g, tab_x2, tab_g2, vk->omega, vk->n_inv, vk->x2_inf) ? 1u : 0u;
+    S c[6];
+    for (int j = 0; j < 6; j++) {
+        for (int i = 0; i < 8; i++) c[j].l[i] = consts[8 * j + i];
+        c[j] = fp_to_mont(c[j]);
     }
-    vk->g[0] = fp_to_mont(gx);
-    vk->g[1] = fp_to_mont(gy);
-    G.x = f_to_mont_any(G.x);
-    G.y = f_to_mont_any(G.y);
-    g2_line_table(G, tab_g2, K);
-    Affine<Fp2<C>> X2;
-    const bool x2_inf = decode_point(x2_xyz, X2);
-    uint32_t bad = 0;
-    if (!x2_inf) {
-        if (!on_curve(X2, K)) bad = 1;
-        g2_line_table(X2, tab_x2, K);
-    }
-    S c[6], w, n = fp_zero<Fr>();
-    for (int i = 0; i < 8; i++) {
-        for (int j = 0; j < 6; j++) c[j].l[i] = consts[8 * j + i];
-        w.l[i] = omega_mont[i];
-        if ((uint32_t)i == (power >> 5)) n.l[i] = 1u << (power & 31);
-    }
-    for (int j = 0; j < 6; j++) c[j] = fp_to_mont(c[j]);
     vk->k1 = c[0];
     vk->k2 = c[1];
     vk->wr = c[5];
-    vk->omega = w;
-    vk->n_inv = fp_inv(fp_to_mont(n));
     vk->w8p[0] = vk->w4p[0] = vk->w3p[0] = fp_one<Fr>();
     for (int i = 1; i < 8; i++) vk->w8p[i] = fp_mul(vk->w8p[i - 1], c[4]);
     for (int i = 1; i < 4; i++) vk->w4p[i] = fp_mul(vk->w4p[i - 1], c[3]);
     for (int i = 1; i < 3; i++) vk->w3p[i] = fp_mul(vk->w3p[i - 1], c[2]);
     vk->power = power;
     vk->n_public = n_public;
-    vk->x2_inf = x2_inf ? 1u : 0u;
-    vk->bad = bad;
 }
 
 // ---- per proof ------------------------------------------------------------------------------------------------------------------------

@@ -11,10 +11,9 @@
 // Where the reference throws — a wrong count and no logger — this returns false. Calls that arrive while a batch of the same key is on the device join
 // the next batch; keys stay resident per vk content until uninstallFused.
 "use strict";
-const path = require("path");
+const { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, pack, refusedCount, makeVerifier: makeVerifierOf } = require("./verify_common.js");
 
-const BN128 = { id: 0, n8: 32, p: 21888242871839275222246405745257275088696311157297823662689037894645226208583n,
-                r: 21888242871839275222246405745257275088548364400416034343698204186575808495617n };
+const BN128 = CURVES.bn128;
 // Fr.w[power] of BN254 is Fr.w[28]^(2^(28 - power)); Fr.w[28] = 5^((r - 1) / 2^28) (ffjavascript: the first non-residue is 5)
 const W28 = 19103219067921713944291392827692070036145651957329286315305642004821462161904n;
 const MESSAGES = { 1: "PROOF VERIFIED SUCCESSFULLY", 0: "Invalid Proof", "-1": "Public inputs are not valid.", "-2": "Proof commitments are not valid",
@@ -23,29 +22,6 @@ const KEY_CONSTS = ["k1", "k2", "w3", "w4", "w8", "wr"];
 const PROOF_POINTS = ["C1", "C2", "W1", "W2"];
 const PROOF_EVALS = ["ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3", "a", "b", "c", "z", "zw", "t1w", "t2w"];
 
-let addon = null;
-function loadAddon() {
-    if (!addon) addon = require(path.join(__dirname, "..", "napi", "zkmi_napi.node"));
-    return addon;
-}
-function big(v) {
-    if (typeof v === "bigint") return v;
-    if (typeof v === "number") return BigInt(v);
-    if (typeof v === "string") return BigInt(v);
-    throw new TypeError("not a field element: " + v);
-}
-function putLE(out, off, v, n8) {
-    for (let i = 0; i < n8; i++) { out[off + i] = Number(v & 0xffn); v >>= 8n; }
-}
-function mod(v, p) { const m = v % p; return m < 0n ? m + p : m; }
-function g1Bytes(o, c, out, off) {
-    const z = o.length > 2 ? o[2] : 1;
-    [o[0], o[1], z].forEach((v, k) => putLE(out, off + k * c.n8, mod(big(v), c.p), c.n8));
-}
-function g2Bytes(o, c, out, off) {
-    const z = o.length > 2 ? o[2] : [1, 0];
-    [o[0], o[1], z].forEach((e, k) => { putLE(out, off + 2 * k * c.n8, mod(big(e[0]), c.p), c.n8); putLE(out, off + (2 * k + 1) * c.n8, mod(big(e[1]), c.p), c.n8); });
-}
 function rootOfUnity(power) {
     let w = W28;
     for (let i = power; i < 28; i++) w = w * w % BN128.r;
@@ -72,34 +48,17 @@ class VerifyingKey {
     get recordBytes() { return 12 * this.c.n8 + 480; }
     // packed records + per-proof verdicts decided on the host (a public outside [0, r) may have no 32-byte form: -1, unless a commitment is bad)
     pack(publicSignalsList, proofs) {
-        const n = proofs.length, c = this.c, rec = this.recordBytes;
-        if (publicSignalsList.length !== n) throw new Error("one publicSignals list per proof");
-        const nSig = n ? publicSignalsList[0].length : this.nPublic;
-        const recs = new Uint8Array(n * rec), pubs = new Uint8Array(n * nSig * 32), pre = new Array(n).fill(null);
-        for (let i = 0; i < n; i++) {
-            const sig = publicSignalsList[i], pr = proofs[i];
-            if (sig.length !== nSig) throw new Error("every proof of a batch needs the same number of public signals");
-            const vals = sig.map(big);
-            if (vals.some((v) => v < 0n || v >= c.r)) pre[i] = -1;
-            else vals.forEach((v, k) => putLE(pubs, (i * nSig + k) * 32, v, 32));
-            PROOF_POINTS.forEach((k, j) => g1Bytes(pr.polynomials[k], c, recs, i * rec + j * 3 * c.n8));
-            PROOF_EVALS.forEach((k, j) => {
-                const v = big(pr.evaluations[k]);        // the device reduces modulo r (Fr.fromObject); the host only what does not fit 32 bytes
-                putLE(recs, i * rec + 12 * c.n8 + 32 * j, v >= 0n && v < (1n << 256n) ? v : mod(v, c.r), 32);
-            });
-        }
-        return { recs, pubs, nSig, pre };
+        const c = this.c;
+        return pack(this, publicSignalsList, proofs, this.recordBytes, (pr, recs, off) => {
+            PROOF_POINTS.forEach((k, j) => g1Bytes(pr.polynomials[k], c, recs, off + j * 3 * c.n8));
+            PROOF_EVALS.forEach((k, j) => frBytes(pr.evaluations[k], c, recs, off + 12 * c.n8 + 32 * j));
+        }, this.nPublic, false);
     }
     async verifyCodes(publicSignalsList, proofs) {
         if (!proofs.length) return [];
         const { recs, pubs, nSig, pre } = this.pack(publicSignalsList, proofs);
         if (nSig !== this.nPublic) {               // the reference tests the count first: -3 whatever the commitments are
-            let refused = false;
-            try { await loadAddon().fflonkVerifyAsync(this.handle, recs, pubs, nSig, proofs.length); } catch (e) {
-                if (!String(e.message).includes(MESSAGES["-3"])) throw e;
-                refused = true;
-            }
-            if (!refused) throw new Error("a wrong number of public signals was not refused");
+            await refusedCount(() => loadAddon().fflonkVerifyAsync(this.handle, recs, pubs, nSig, proofs.length), MESSAGES["-3"]);
             return proofs.map(() => -3);
         }
         const out = await loadAddon().fflonkVerifyAsync(this.handle, recs, pubs, nSig, proofs.length);
@@ -115,48 +74,12 @@ class VerifyingKey {
 }
 
 // snarkjs.fflonk.verify on the device: keys resident per vk content; concurrent calls of one key (and one public-signal count) coalesce into batches
-function makeVerifier(snarkjs, options) {
-    const keys = new Map();                 // JSON of the vk -> { key, queues: Map(nSig -> { pending, busy }) }
-    const stats = { calls: 0, batches: 0 };
-    function entryOf(vk) {
-        const id = JSON.stringify(vk, (k, v) => (typeof v === "bigint" ? v.toString() : v));
-        let e = keys.get(id);
-        if (!e) { e = { key: new VerifyingKey(vk, options), queues: new Map() }; keys.set(id, e); }
-        return e;
-    }
-    function pump(e, q) {
-        if (q.busy || !q.pending.length) return;
-        const batch = q.pending.splice(0, q.pending.length);
-        q.busy = true;
-        stats.batches++;
-        e.key.verifyCodes(batch.map((b) => b.pubs), batch.map((b) => b.proof)).then((codes) => {
-            batch.forEach((b, i) => {
-                const code = codes[i];
-                if (b.logger) {
-                    if (code === 1) b.logger.info(MESSAGES[1]); else if (code === 0) b.logger.warn(MESSAGES[0]); else b.logger.error(MESSAGES[code]);
-                    if (code === 0 || code === 1) b.logger.info("FFLONK VERIFIER FINISHED");
-                }
-                b.resolve(code === 1);
-            });
-        }, (err) => batch.forEach((b) => b.reject(err))).then(() => { q.busy = false; pump(e, q); });
-    }
-    async function verify(vk, publicSignals, proof, logger) {
-        stats.calls++;
-        const e = entryOf(vk);
-        if (logger) logger.info("FFLONK VERIFIER STARTED");
-        const nSig = publicSignals.length;
-        let q = e.queues.get(nSig);
-        if (!q) { q = { pending: [], busy: false }; e.queues.set(nSig, q); }
-        return new Promise((resolve, reject) => {
-            q.pending.push({ pubs: publicSignals, proof, logger, resolve, reject });
-            setImmediate(() => pump(e, q));          // let the calls of this turn of the event loop join the batch
-        });
-    }
-    function release() {
-        for (const e of keys.values()) { try { e.key.release(); } catch (err) { /* already released */ } }
-        keys.clear();
-    }
-    return { verify, release, stats, keys };
-}
+const makeVerifier = makeVerifierOf(VerifyingKey, {
+    start: "FFLONK VERIFIER STARTED",
+    log(logger, code) {
+        if (code === 1) logger.info(MESSAGES[1]); else if (code === 0) logger.warn(MESSAGES[0]); else logger.error(MESSAGES[code]);
+        if (code === 0 || code === 1) logger.info("FFLONK VERIFIER FINISHED");
+    },
+});
 
 module.exports = { VerifyingKey, makeVerifier, MESSAGES };

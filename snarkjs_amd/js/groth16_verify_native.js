@@ -8,40 +8,9 @@
 // return value and logger messages (src/groth16_verify.js:26-87); calls that arrive while a batch of the same key is on the device join the next batch;
 // keys stay resident per vk content until uninstallFused.
 "use strict";
-const path = require("path");
+const { CURVES, loadAddon, g1Bytes, g2Bytes, pack, makeVerifier: makeVerifierOf } = require("./verify_common.js");
 
-const CURVES = {
-    bn128: { id: 0, n8: 32, p: 21888242871839275222246405745257275088696311157297823662689037894645226208583n,
-             r: 21888242871839275222246405745257275088548364400416034343698204186575808495617n },
-    bls12381: { id: 1, n8: 48, p: 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaabn,
-                r: 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001n },
-};
 const MESSAGES = { 1: "OK!", 0: "Invalid proof", "-1": "Public inputs are not valid.", "-2": "Proof commitments are not valid." };
-
-let addon = null;
-function loadAddon() {
-    if (!addon) addon = require(path.join(__dirname, "..", "napi", "zkmi_napi.node"));
-    return addon;
-}
-// unstringifyBigInts of one value: decimal or "0x" string, number or bigint
-function big(v) {
-    if (typeof v === "bigint") return v;
-    if (typeof v === "number") return BigInt(v);
-    if (typeof v === "string") return BigInt(v);
-    throw new TypeError("not a field element: " + v);
-}
-function putLE(out, off, v, n8) {
-    for (let i = 0; i < n8; i++) { out[off + i] = Number(v & 0xffn); v >>= 8n; }
-}
-function mod(v, p) { const m = v % p; return m < 0n ? m + p : m; }
-function g1Bytes(o, c, out, off) {
-    const z = o.length > 2 ? o[2] : 1;
-    [o[0], o[1], z].forEach((v, k) => putLE(out, off + k * c.n8, mod(big(v), c.p), c.n8));
-}
-function g2Bytes(o, c, out, off) {
-    const z = o.length > 2 ? o[2] : [1, 0];
-    [o[0], o[1], z].forEach((e, k) => { putLE(out, off + 2 * k * c.n8, mod(big(e[0]), c.p), c.n8); putLE(out, off + (2 * k + 1) * c.n8, mod(big(e[1]), c.p), c.n8); });
-}
 
 class VerifyingKey {
     constructor(vk, options) {
@@ -60,22 +29,12 @@ class VerifyingKey {
     }
     // packed records + per-proof verdicts decided on the host (a public outside [0, r) has no 32-byte form: -1, as publicInputsAreValid)
     pack(publicSignalsList, proofs) {
-        const n = proofs.length, c = this.c, rec = 12 * c.n8;
-        if (publicSignalsList.length !== n) throw new Error("one publicSignals list per proof");
-        const nSig = n ? publicSignalsList[0].length : 0;
-        if (nSig > this.nPublic) throw new Error(nSig + " public signals for a key with nPublic = " + this.nPublic);
-        const recs = new Uint8Array(n * rec), pubs = new Uint8Array(n * nSig * 32), pre = new Array(n).fill(null);
-        for (let i = 0; i < n; i++) {
-            const sig = publicSignalsList[i], pr = proofs[i];
-            if (sig.length !== nSig) throw new Error("every proof of a batch needs the same number of public signals");
-            const vals = sig.map(big);
-            if (vals.some((v) => v < 0n || v >= c.r)) pre[i] = -1;
-            else vals.forEach((v, k) => putLE(pubs, (i * nSig + k) * 32, v, 32));
-            g1Bytes(pr.pi_a, c, recs, i * rec);
-            g2Bytes(pr.pi_b, c, recs, i * rec + 3 * c.n8);
-            g1Bytes(pr.pi_c, c, recs, i * rec + 9 * c.n8);
-        }
-        return { recs, pubs, nSig, pre };
+        const c = this.c;
+        return pack(this, publicSignalsList, proofs, 12 * c.n8, (pr, recs, off) => {
+            g1Bytes(pr.pi_a, c, recs, off);
+            g2Bytes(pr.pi_b, c, recs, off + 3 * c.n8);
+            g1Bytes(pr.pi_c, c, recs, off + 9 * c.n8);
+        }, 0, true);
     }
     async verifyCodes(publicSignalsList, proofs) {
         if (!proofs.length) return [];
@@ -93,45 +52,9 @@ class VerifyingKey {
 }
 
 // snarkjs.groth16.verify on the device: keys resident per vk content; concurrent calls of one key (and one public-signal count) coalesce into batches
-function makeVerifier(snarkjs, options) {
-    const keys = new Map();                 // JSON of the vk -> { key, queues: Map(nSig -> { pending, busy }) }
-    const stats = { calls: 0, batches: 0 };
-    function entryOf(vk) {
-        const id = JSON.stringify(vk, (k, v) => (typeof v === "bigint" ? v.toString() : v));
-        let e = keys.get(id);
-        if (!e) { e = { key: new VerifyingKey(vk, options), queues: new Map() }; keys.set(id, e); }
-        return e;
-    }
-    function pump(e, q) {
-        if (q.busy || !q.pending.length) return;
-        const batch = q.pending.splice(0, q.pending.length);
-        q.busy = true;
-        stats.batches++;
-        e.key.verifyCodes(batch.map((b) => b.pubs), batch.map((b) => b.proof)).then((codes) => {
-            batch.forEach((b, i) => {
-                const code = codes[i];
-                if (b.logger) { if (code === 1) b.logger.info(MESSAGES[1]); else b.logger.error(MESSAGES[code]); }
-                b.resolve(code === 1);
-            });
-        }, (err) => batch.forEach((b) => b.reject(err))).then(() => { q.busy = false; pump(e, q); });
-    }
-    async function verify(vk, publicSignals, proof, logger) {
-        stats.calls++;
-        const e = entryOf(vk);
-        const nSig = publicSignals.length;
-        if (nSig > e.key.nPublic) throw new TypeError("more public signals than the key's IC points");      // the reference fails reading IC[i + 1]
-        let q = e.queues.get(nSig);
-        if (!q) { q = { pending: [], busy: false }; e.queues.set(nSig, q); }
-        return new Promise((resolve, reject) => {
-            q.pending.push({ pubs: publicSignals, proof, logger, resolve, reject });
-            setImmediate(() => pump(e, q));          // let the calls of this turn of the event loop join the batch
-        });
-    }
-    function release() {
-        for (const e of keys.values()) { try { e.key.release(); } catch (err) { /* already released */ } }
-        keys.clear();
-    }
-    return { verify, release, stats, keys };
-}
+const makeVerifier = makeVerifierOf(VerifyingKey, {
+    log(logger, code) { if (code === 1) logger.info(MESSAGES[1]); else logger.error(MESSAGES[code]); },
+    guard(key, nSig) { if (nSig > key.nPublic) throw new TypeError("more public signals than the key's IC points"); },      // the reference fails reading IC[i + 1]
+});
 
 module.exports = { VerifyingKey, makeVerifier, MESSAGES };

@@ -983,6 +983,48 @@ static napi_value js_shm_unlink(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- what the three verifiers' bindings share --------------------------------------------------------------------------------------------------- */
+static napi_value vk_handle_value(napi_env env, int rc, uint64_t h) {          /* the return value of a *VkLoad */
+    if (rc) return throw_zkmi(env, rc);
+    napi_value v;
+    NAPI_OK(napi_create_double(env, (double)h, &v));
+    return v;
+}
+static napi_value vk_release_common(napi_env env, napi_callback_info info, int (*release)(uint64_t)) {
+    ARGS(1);
+    double h;
+    if (get_f64(env, argv[0], &h)) BAD_ARG();
+    int rc = ZK_CALL(release((uint64_t)h));
+    if (rc) return throw_zkmi(env, rc);
+    return NULL;
+}
+static size_t plonk_record_bytes(int curve) { return 27 * (curve == ZKMI_CURVE_BN128 ? 32 : 48) + 192; }
+static size_t fflonk_record_bytes(int curve) { return 12 * (curve == ZKMI_CURVE_BN128 ? 32 : 48) + 480; }
+/* (handle, records, publics, nSignals, n) -> Promise<Uint8Array(n)> through job kind `kind`. With vk_info / record_bytes the record buffer must have
+ * the size of the handle's own curve; Groth16 passes NULL and leaves the record length unchecked. */
+static napi_value verify_async_common(napi_env env, napi_callback_info info, int kind, const char* name, int (*vk_info)(uint64_t, int*, uint32_t*),
+                                      size_t (*record_bytes)(int)) {
+    ARGS(5);
+    double h, ns, n;
+    pages_t pr, pu;
+    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
+    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
+    if (record_bytes) {
+        int curve = 0; uint32_t np = 0;
+        int rc = ZK_CALL(vk_info((uint64_t)h, &curve, &np));
+        if (rc) return throw_zkmi(env, rc);
+        if (pr.len[0] != (size_t)n * record_bytes(curve)) BAD_ARG();
+    }
+    uint8_t* out;
+    napi_value res = new_u8(env, (size_t)n, &out);
+    if (!res) BAD_ARG();
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    if (!j) BAD_ARG();
+    j->kind = kind; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
+    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
+    return job_queue(env, j, name, argv, 5, res);
+}
+
 /* ---- Groth16 verification (src/groth16_verify.js:26-87; include/zkmi.h zkmi_groth16_vk_load / _verify_batch / _vk_release) ----------------------
  * groth16VkLoad(curve, alpha1Xyz, beta2Xyz, gamma2Xyz, delta2Xyz, icXyz, nPublic) -> handle: points as (x, y, z) in standard form, little-endian.
  * groth16VerifyAsync(handle, proofsXyz, publics, nSignals, n) -> Promise<Uint8Array(n)>: verdict bytes (int8: 1 OK, 0 invalid, -1 publics, -2 points);
@@ -999,34 +1041,10 @@ static napi_value js_groth16_vk_load(napi_env env, napi_callback_info info) {
         d.len[0] != 6 * n8 || ic.len[0] != ((size_t)np + 1) * 3 * n8) BAD_ARG();
     uint64_t h = 0;
     int rc = ZK_CALL(zkmi_groth16_vk_load(curve, a.ptr[0], b.ptr[0], g.ptr[0], d.ptr[0], ic.ptr[0], (uint32_t)np, &h));
-    if (rc) return throw_zkmi(env, rc);
-    napi_value v;
-    NAPI_OK(napi_create_double(env, (double)h, &v));
-    return v;
+    return vk_handle_value(env, rc, h);
 }
-static napi_value js_groth16_verify_async(napi_env env, napi_callback_info info) {
-    ARGS(5);
-    double h, ns, n;
-    pages_t pr, pu;
-    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
-    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
-    uint8_t* out;
-    napi_value res = new_u8(env, (size_t)n, &out);
-    if (!res) BAD_ARG();
-    job_t* j = (job_t*)calloc(1, sizeof *j);
-    if (!j) BAD_ARG();
-    j->kind = 8; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
-    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
-    return job_queue(env, j, "zkmi.groth16Verify", argv, 5, res);
-}
-static napi_value js_groth16_vk_release(napi_env env, napi_callback_info info) {
-    ARGS(1);
-    double h;
-    if (get_f64(env, argv[0], &h)) BAD_ARG();
-    int rc = ZK_CALL(zkmi_groth16_vk_release((uint64_t)h));
-    if (rc) return throw_zkmi(env, rc);
-    return NULL;
-}
+static napi_value js_groth16_verify_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 8, "zkmi.groth16Verify", NULL, NULL); }
+static napi_value js_groth16_vk_release(napi_env env, napi_callback_info info) { return vk_release_common(env, info, zkmi_groth16_vk_release); }
 
 /* ---- PLONK verification (src/plonk_verify.js:29-123; include/zkmi.h zkmi_plonk_vk_load / _verify_batch / _vk_release) ---------------------------
  * plonkVkLoad(curve, g1PointsXyz (Qm Ql Qr Qo Qc S1 S2 S3), x2Xyz, k1, k2, power, nPublic) -> handle.
@@ -1044,38 +1062,10 @@ static napi_value js_plonk_vk_load(napi_env env, napi_callback_info info) {
         k1.len[0] != 32 || k2.len[0] != 32) BAD_ARG();
     uint64_t h = 0;
     int rc = ZK_CALL(zkmi_plonk_vk_load(curve, g.ptr[0], x.ptr[0], k1.ptr[0], k2.ptr[0], (uint32_t)power, (uint32_t)np, &h));
-    if (rc) return throw_zkmi(env, rc);
-    napi_value v;
-    NAPI_OK(napi_create_double(env, (double)h, &v));
-    return v;
+    return vk_handle_value(env, rc, h);
 }
-static napi_value js_plonk_verify_async(napi_env env, napi_callback_info info) {
-    ARGS(5);
-    double h, ns, n;
-    pages_t pr, pu;
-    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
-    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
-    int curve = 0; uint32_t np = 0;                       /* the record buffer must have the size of the handle's own curve */
-    int rc = ZK_CALL(zkmi_plonk_vk_info((uint64_t)h, &curve, &np));
-    if (rc) return throw_zkmi(env, rc);
-    if (pr.len[0] != (size_t)n * (27 * (curve == ZKMI_CURVE_BN128 ? 32 : 48) + 192)) BAD_ARG();
-    uint8_t* out;
-    napi_value res = new_u8(env, (size_t)n, &out);
-    if (!res) BAD_ARG();
-    job_t* j = (job_t*)calloc(1, sizeof *j);
-    if (!j) BAD_ARG();
-    j->kind = 9; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
-    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
-    return job_queue(env, j, "zkmi.plonkVerify", argv, 5, res);
-}
-static napi_value js_plonk_vk_release(napi_env env, napi_callback_info info) {
-    ARGS(1);
-    double h;
-    if (get_f64(env, argv[0], &h)) BAD_ARG();
-    int rc = ZK_CALL(zkmi_plonk_vk_release((uint64_t)h));
-    if (rc) return throw_zkmi(env, rc);
-    return NULL;
-}
+static napi_value js_plonk_verify_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 9, "zkmi.plonkVerify", zkmi_plonk_vk_info, plonk_record_bytes); }
+static napi_value js_plonk_vk_release(napi_env env, napi_callback_info info) { return vk_release_common(env, info, zkmi_plonk_vk_release); }
 
 /* ---- FFLONK verification (src/fflonk_verify.js:28-137; include/zkmi.h zkmi_fflonk_vk_load / _verify_batch / _vk_info / _vk_release), BN254 only ---
  * fflonkVkLoad(curve, c0Xyz, x2Xyz, consts (k1 k2 w3 w4 w8 wr), power, nPublic) -> handle.
@@ -1093,30 +1083,9 @@ static napi_value js_fflonk_vk_load(napi_env env, napi_callback_info info) {
     if (np < 0 || np > 1e8 || power < 0 || power > 32 || c0.n != 1 || x.n != 1 || k.n != 1 || c0.len[0] != 3 * n8 || x.len[0] != 6 * n8 || k.len[0] != 192) BAD_ARG();
     uint64_t h = 0;
     int rc = ZK_CALL(zkmi_fflonk_vk_load(curve, c0.ptr[0], x.ptr[0], k.ptr[0], (uint32_t)power, (uint32_t)np, &h));          /* refuses BLS12-381 */
-    if (rc) return throw_zkmi(env, rc);
-    napi_value v;
-    NAPI_OK(napi_create_double(env, (double)h, &v));
-    return v;
+    return vk_handle_value(env, rc, h);
 }
-static napi_value js_fflonk_verify_async(napi_env env, napi_callback_info info) {
-    ARGS(5);
-    double h, ns, n;
-    pages_t pr, pu;
-    if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
-    if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
-    int curve = 0; uint32_t np = 0;                       /* the record buffer must have the size of the handle's own curve */
-    int rc = ZK_CALL(zkmi_fflonk_vk_info((uint64_t)h, &curve, &np));
-    if (rc) return throw_zkmi(env, rc);
-    if (pr.len[0] != (size_t)n * (12 * (curve == ZKMI_CURVE_BN128 ? 32 : 48) + 480)) BAD_ARG();
-    uint8_t* out;
-    napi_value res = new_u8(env, (size_t)n, &out);
-    if (!res) BAD_ARG();
-    job_t* j = (job_t*)calloc(1, sizeof *j);
-    if (!j) BAD_ARG();
-    j->kind = 10; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
-    if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
-    return job_queue(env, j, "zkmi.fflonkVerify", argv, 5, res);
-}
+static napi_value js_fflonk_verify_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 10, "zkmi.fflonkVerify", zkmi_fflonk_vk_info, fflonk_record_bytes); }
 static napi_value js_fflonk_vk_info(napi_env env, napi_callback_info info) {
     ARGS(1);
     double h;
@@ -1132,14 +1101,7 @@ static napi_value js_fflonk_vk_info(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_set_named_property(env, o, "nPublic", p));
     return o;
 }
-static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) {
-    ARGS(1);
-    double h;
-    if (get_f64(env, argv[0], &h)) BAD_ARG();
-    int rc = ZK_CALL(zkmi_fflonk_vk_release((uint64_t)h));
-    if (rc) return throw_zkmi(env, rc);
-    return NULL;
-}
+static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) { return vk_release_common(env, info, zkmi_fflonk_vk_release); }
 
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {

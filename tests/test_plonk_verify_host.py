@@ -31,7 +31,7 @@ def expected(tag, vk, pubs, proof):
 def tool():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("plonk_verify.cuh", "pairing.cuh", "pairing_host.hpp", "curve.cuh", "field.cuh", "host_field.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("plonk_verify.cuh", "kzg_verify.cuh", "pairing.cuh", "pairing_host.hpp", "curve.cuh", "field.cuh", "host_field.hpp")]
     if not os.path.exists(TOOL) or any(os.path.getmtime(d) > os.path.getmtime(TOOL) for d in deps):
         os.makedirs(os.path.dirname(TOOL), exist_ok=True)
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O0", "-std=c++17", "-I" + CSRC, SRC, "-o", TOOL])
