@@ -275,6 +275,17 @@ int zkmi_fflonk_verify_batch(uint64_t vk_handle, const uint8_t* proofs, const ui
 int zkmi_fflonk_vk_release(uint64_t vk_handle);
 /* The curve (ZKMI_CURVE_*) and nPublic of a loaded FFLONK verifying key, so that a caller can size a batch's buffers. */
 int zkmi_fflonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public);
+/* The aggregated check of a batch under one PLONK / FFLONK key: "are ALL of these valid?" by ONE pairing check. Inputs and refusals
+ * as zkmi_*_verify_batch; seed = 32 bytes the maker of the proofs could not predict. r_i = the first 16 bytes, little-endian, of
+ * Keccak-256(seed | LE64(i)) with bit 127 set; codes[i] = the input checks' code of proof i (-2 / -1 as above) or 1: its pair entered the sums
+ * S_P = sum r_i P_i, S_Q = sum r_i Q_i; *ok = 1 exactly when every code is 1 and e(-S_P, T0) e(S_Q, T1) == 1 (PLONK: A1, B1, X_2, [1]_2; FFLONK: A1,
+ * W2, [1]_2, X_2). An empty batch is ok. If every per-proof verdict is 1, ok is 1; if one is not, ok is 0 except with probability about 2^-127
+ * over the seed (proof points in G1; on BLS12-381 the sums are multiplied by the G1 cofactor first, so a point outside G1 enters through its G1
+ * component only). */
+int zkmi_plonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                int* ok);
+int zkmi_fflonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                 int* ok);
 /* Multi-GPU proof (BASELINE configs[2]: MSMs sharded across the GPUs of a node). Every rank loads the shard of the
  * key that holds the witness-side bases of the variables [var_lo, var_hi) (sections 5-8) and the H bases [h_lo, h_hi) (section 9);
  * the section pointers of `zkey` are those of the FULL sections, the library slices them. zkmi_groth16_sums_dev runs the device

@@ -85,6 +85,16 @@ double zkmi_plonk_verify_last_ms(void);
 int zkmi_fflonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const uint8_t* publics, uint32_t n_signals, uint8_t* out);
 /* Device time of the verification kernel of the last zkmi_fflonk_verify_batch, in milliseconds; -1: none yet. */
 double zkmi_fflonk_verify_last_ms(void);
+/* zkmi_*_verify_aggregate with its two sums reported: sums = S_P.x S_P.y S_Q.x S_Q.y (n8q bytes each, affine, standard form, before the cofactor
+ * multiplication; the point at infinity all-zero): 4 n8q bytes. */
+int zkmi_plonk_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                   int* ok, uint8_t* sums);
+int zkmi_fflonk_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                    int* ok, uint8_t* sums);
+/* Device time of the lane phase | the reduction | the tail of the last aggregated batch, in milliseconds (three doubles; -1 where the verifier's
+ * last batch was not an aggregated one). After an aggregated batch zkmi_*_verify_last_ms reports the three together. */
+int zkmi_plonk_aggregate_phase_ms(double* lane_reduce_tail);
+int zkmi_fflonk_aggregate_phase_ms(double* lane_reduce_tail);
 
 #ifdef __cplusplus
 }

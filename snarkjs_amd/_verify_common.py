@@ -1,7 +1,9 @@
 """What the three batch verifiers (groth16_verify, plonk_verify, fflonk_verify) share on the host: field-element and point encoding, the
-public-signal half of a packed batch, the size checks around a *_verify_batch call, the trace decoder, the cache behind verify() /
+public-signal half of a packed batch, the size checks around a *_verify_batch call, the trace decoder, the aggregated check
+of the two KZG verifiers (verify_all / verify_all_raw / verify_many_fast), the cache behind verify() /
 release_all() (each module passes its own dict) and the zkey header reader of the two vk_from_zkey. Needs no device except root()."""
 import json
+import os
 import struct
 
 import numpy as np
@@ -88,6 +90,67 @@ def verify_raw(key, verify_batch, rec, proofs_u8, publics_u8, n_signals, n, n_si
     pub = publics_u8 if publics_u8.size else np.zeros(1, np.uint8)
     zkmi.check(verify_batch(key.handle, zkmi.ptr(proofs_u8), zkmi.ptr(pub), n_signals, n, zkmi.ptr(out)))
     return out[:n]
+
+
+def new_seed(seed):
+    """the 32 seed bytes of an aggregated check: drawn from the OS unless given (reproducibility; whoever made the proofs must not know it)"""
+    if seed is None:
+        return os.urandom(32)
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed of an aggregated check is 32 bytes")
+    return seed
+
+
+def verify_all_raw(key, verify_aggregate, rec, proofs_u8, publics_u8, n_signals, n, n_sig_empty, seed, sums=None):
+    """(ok, codes) of packed records by the library's *_verify_aggregate of key's protocol (or, with sums = a uint8 array of 4 n8 bytes, its
+    *_aggregate_trace_dev): ONE pairing check for the batch; codes[i] is proof i's input-check code or 1 (entered the sums)"""
+    proofs_u8, publics_u8 = zkmi.u8(proofs_u8), zkmi.u8(publics_u8)
+    if n is None:
+        n = proofs_u8.size // rec
+    if n_signals is None:
+        n_signals = publics_u8.size // (32 * n) if n else n_sig_empty
+    if proofs_u8.size != n * rec or publics_u8.size != n * n_signals * 32:
+        raise ValueError("packed arrays do not match n and n_signals")
+    sd = np.frombuffer(new_seed(seed), np.uint8).copy()
+    out = np.zeros(max(n, 1), np.int8)
+    pub = publics_u8 if publics_u8.size else np.zeros(1, np.uint8)
+    prf = proofs_u8 if proofs_u8.size else np.zeros(1, np.uint8)
+    ok = zkmi.C.c_int(0)
+    extra = () if sums is None else (zkmi.ptr(sums),)
+    zkmi.check(verify_aggregate(key.handle, zkmi.ptr(prf), zkmi.ptr(pub), n_signals, n, zkmi.ptr(sd), zkmi.ptr(out), zkmi.C.byref(ok), *extra))
+    return bool(ok.value), out[:n]
+
+
+def verify_all(key, public_signals_list, proofs, seed, count_message):
+    """are all of these valid? False where a public signal is out of range (caught while packing) or the number of signals is wrong (refused by
+    the device call as a whole, as in verify_codes)"""
+    recs, pubs, n_sig, pre = key.pack(public_signals_list, proofs)
+    if proofs and n_sig != key.n_public:
+        refused_count(key, recs, pubs, n_sig, len(proofs), count_message)
+        return False
+    if any(c is not None for c in pre):
+        return False
+    return key.verify_all_raw(recs, pubs, n_sig, len(proofs), seed)[0]
+
+
+def verify_many_fast(key, public_signals_list, proofs, seed, count_message):
+    """verify_many for mostly honest traffic: all-valid by the aggregated check, else the per-proof answer that names the culprits"""
+    if verify_all(key, public_signals_list, proofs, seed, count_message):
+        return [True] * len(proofs)
+    return key.verify_many(public_signals_list, proofs)
+
+
+def aggregate_trace(key, aggregate_trace_dev, public_signals_list, proofs, seed):
+    """*_aggregate_trace_dev: (ok, codes, S_P, S_Q) with a sum as (x, y) or None for the point at infinity"""
+    recs, pubs, n_sig, pre = key.pack(public_signals_list, proofs)
+    if any(c is not None for c in pre):
+        raise ValueError("a public signal is outside [0, r)")
+    n8 = key.n8
+    sums = np.zeros(4 * n8, np.uint8)
+    ok, codes = verify_all_raw(key, aggregate_trace_dev, key.record_bytes, recs, pubs, n_sig, len(proofs), key.n_public, seed, sums)
+    v = [int.from_bytes(sums[i * n8:(i + 1) * n8].tobytes(), "little") for i in range(4)]
+    return ok, codes, (None if (v[0], v[1]) == (0, 0) else (v[0], v[1])), (None if (v[2], v[3]) == (0, 0) else (v[2], v[3]))
 
 
 def refused_count(key, recs, pubs, n_sig, n, message):

@@ -114,7 +114,11 @@ template <class C> ZK_DEV bool fflonk_point(const uint32_t* xyz, Affine<Fp<C>>& 
 // proof record: C1 C2 W1 W2 as (x, y, z) (12 Fq) | ql qr qm qo qc s1 s2 s3 a b c z zw t1w t2w (8 words each), standard form;
 // pubs: vk.n_public x 8 words. tr (may be null) receives the intermediate values of a proof that passes the input checks.
 template <class C> constexpr int fflonk_record_words() { return 12 * C::N + 8 * FFLONK_EVALS; }
-template <class C> ZK_PAIR_OP int fflonk_verify_one(const uint32_t* rec, const uint32_t* pubs, const FflonkVkView<C>& V, const PairingConsts<C>* K, FflonkTrace<C>* tr) {
+// With AGG the check stops before the pairing and hands over its two G1 points, A1 and W2, instead (the aggregated check, kzg_aggregate.cuh; KzgPair:
+// kzg_verify.cuh); the code is then FFLONKV_VALID for "the input checks passed". Without it (the default:
+// the per-proof kernel) the function is what it was.
+template <class C, bool AGG = false>
+ZK_PAIR_OP int fflonk_verify_one(const uint32_t* rec, const uint32_t* pubs, const FflonkVkView<C>& V, const PairingConsts<C>* K, FflonkTrace<C>* tr, KzgPair<C>* pair = nullptr) {
     using Fr = typename PairingCfg<C>::Fr;
     using S = Fp<Fr>;
     constexpr int N = C::N;
@@ -285,14 +289,19 @@ template <class C> ZK_PAIR_OP int fflonk_verify_one(const uint32_t* rec, const u
         const Fp<C> p[4] = {fp_from_mont(ax), fp_from_mont(ay), fp_from_mont(W2.x), fp_from_mont(W2.y)};
         for (int i = 0; i < N; i++) { tr->a1[i] = p[0].l[i]; tr->a1[N + i] = p[1].l[i]; tr->b1[i] = p[2].l[i]; tr->b1[N + i] = p[3].l[i]; }
     }
-    // e(-A1, [1]_2) e(W2, X_2) == 1 (:539-551); pairs are passed as (-px, py)
-    const FixedPair<C> f0{V.tab_g2, fp_neg(ax), fp_neg(ay), a_fin};
-    const FixedPair<C> f1{V.tab_x2, fp_neg(W2.x), W2.y, w2_fin && !vk.x2_inf};
-    Affine<Fp2<C>> none;
-    f_set_zero(none.x);
-    f_set_zero(none.y);
-    const Fp12<C> f = miller_multi(none, ax, ay, false, f0, f1, K);
-    return f12_is_one(final_exp(f, K)) ? FFLONKV_VALID : FFLONKV_INVALID;
+    if constexpr (AGG) {
+        *pair = KzgPair<C>{ax, ay, W2.x, W2.y, a_fin, w2_fin};
+        return FFLONKV_VALID;
+    } else {
+        // e(-A1, [1]_2) e(W2, X_2) == 1 (:539-551); pairs are passed as (-px, py)
+        const FixedPair<C> f0{V.tab_g2, fp_neg(ax), fp_neg(ay), a_fin};
+        const FixedPair<C> f1{V.tab_x2, fp_neg(W2.x), W2.y, w2_fin && !vk.x2_inf};
+        Affine<Fp2<C>> none;
+        f_set_zero(none.x);
+        f_set_zero(none.y);
+        const Fp12<C> f = miller_multi(none, ax, ay, false, f0, f1, K);
+        return f12_is_one(final_exp(f, K)) ? FFLONKV_VALID : FFLONKV_INVALID;
+    }
 }
 
 }  // namespace zkmi

@@ -7,11 +7,13 @@
 //
 // BLS12-381 is refused: the reference's fflonk.setup / fflonk.prove do not work on it, so there is no verdict to hold one to.
 //
+// The aggregated check of a whole batch (k_fflonk_agg_lane here, then the reduction and the tail of aggregate_host.hpp): kzg_aggregate.cuh.
+//
 // Isolation from the provers and the other verifiers, and the one coupling through hipFree that remains: verify_host.hpp. This verifier's
 // context is fctx().
 #include <stddef.h>
 #include <string.h>
-#include "verify_host.hpp"
+#include "aggregate_host.hpp"
 #include "fflonk_verify.cuh"
 
 namespace zkmi {
@@ -32,13 +34,23 @@ template <class C> __global__ void __launch_bounds__(VERIFY_BLOCK) k_fflonk_veri
     out[i] = (int8_t)fflonk_verify_one(recs + i * fflonk_record_words<C>(), pubs + i * 8 * V.vk->n_public, V, K, tr);
 }
 
+// The lane phase of the aggregated check (kzg_aggregate.cuh): fflonk_verify_one up to its two points, then r_i times the lane's pair; the block's 64 pairs are added
+// in LDS and leave as one (aggregate_host.hpp agg_lane).
+template <class C> __global__ void __launch_bounds__(VERIFY_BLOCK) k_fflonk_agg_lane(const uint32_t* recs, const uint32_t* pubs, uint64_t n, FflonkVkView<C> V,
+                                                                                           const PairingConsts<C>* K, AggSeed seed, int8_t* out, AggPair<C>* parts) {
+    __shared__ AggPair<C> sh[VERIFY_BLOCK];
+    agg_lane<C>(sh, n, seed, out, parts, [&](uint64_t i, KzgPair<C>* pr) {
+        return fflonk_verify_one<C, true>(recs + i * fflonk_record_words<C>(), pubs + i * 8 * V.vk->n_public, V, K, (FflonkTrace<C>*)nullptr, pr);
+    });
+}
+
 struct FflonkVkEntry {
     int curve = 0;
     uint32_t n_public = 0;
     void* blocks[2] = {nullptr, nullptr};                  // FflonkVk | the line tables of X_2 and of the G2 generator
 };
-VerifyCtx<FflonkVkEntry>& fctx() {
-    static VerifyCtx<FflonkVkEntry> v;
+KzgVerifyCtx<FflonkVkEntry>& fctx() {
+    static KzgVerifyCtx<FflonkVkEntry> v;
     return v;
 }
 
@@ -100,6 +112,39 @@ int verify_entry(const char* who, uint64_t vk_handle, const uint8_t* proofs, con
     return verify_batch<Bn254Fq>(e, proofs, publics, n, verdicts, trace_out);
 }
 
+template <class C> int aggregate_batch(const FflonkVkEntry& e, const uint8_t* proofs, const uint8_t* publics, size_t n, const uint8_t* seed, int8_t* codes, int* ok, uint8_t* sums) {
+    auto& v = fctx();
+    const PairingConsts<C>* K;
+    ZK_TRY(v.consts<C>(&K));
+    const Line<C>* tabs = (const Line<C>*)e.blocks[1];
+    const FflonkVkView<C> V{(const FflonkVk<C>*)e.blocks[0], tabs, tabs + miller_lines<C>()};
+    AggSeed sd;
+    memcpy(sd.w, seed, 32);
+    const uint32_t* x2_inf = (const uint32_t*)((const uint8_t*)e.blocks[0] + offsetof(FflonkVk<C>, x2_inf));
+    return run_aggregate<C>(v, proofs, n * 4 * fflonk_record_words<C>(), publics, n * e.n_public * 32, n, codes, ok, sums, tabs + miller_lines<C>(), tabs, x2_inf, 0, K,
+                                   [&](unsigned blocks, AggPair<C>* parts) {
+        hipLaunchKernelGGL(k_fflonk_agg_lane<C>, dim3(blocks), dim3(VERIFY_BLOCK), 0, v.stream, (const uint32_t*)v.in_a.p, (const uint32_t*)v.in_b.p, (uint64_t)n, V, K, sd,
+                           (int8_t*)v.out.p, parts);
+    });
+}
+
+// the aggregated entry: the same refusals as verify_entry; an empty batch is ok; sums (may be null) is zeroed first
+int aggregate_entry(const char* who, uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t* seed, int8_t* codes, int* ok,
+                    uint8_t* sums) {
+    ZK_TRY(fctx().begin());
+    const FflonkVkEntry* found = fctx().find(vk_handle, who);
+    if (!found) return ZKMI_ERR_INVALID;
+    const FflonkVkEntry& e = *found;
+    if (n_signals != e.n_public) return fail(ZKMI_ERR_INVALID, "Number of public signals does not match with vk");
+    if (!seed || !ok) return fail(ZKMI_ERR_INVALID, std::string(who) + ": null argument");
+    if (sums) memset(sums, 0, e.curve == ZKMI_CURVE_BN128 ? 128 : 192);
+    *ok = 1;
+    if (n == 0) return ZKMI_OK;
+    *ok = 0;
+    if (!proofs || !codes || (n_signals && !publics)) return fail(ZKMI_ERR_INVALID, std::string(who) + ": null argument");
+    return aggregate_batch<Bn254Fq>(e, proofs, publics, n, seed, codes, ok, sums);
+}
+
 }  // namespace
 }  // namespace zkmi
 
@@ -127,6 +172,23 @@ int zkmi_fflonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const
     if (!out) return fail(ZKMI_ERR_INVALID, "fflonk_verify_trace_dev: null argument");
     int8_t verdict = 0;
     return verify_entry("fflonk_verify_trace_dev", vk_handle, proof, publics, n_signals, 1, &verdict, out);
+}
+
+int zkmi_fflonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes, int* ok) {
+    std::lock_guard<std::mutex> g(fctx().mu);
+    return aggregate_entry("fflonk_verify_aggregate", vk_handle, proofs, publics, n_signals, n, seed, codes, ok, nullptr);
+}
+
+int zkmi_fflonk_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes, int* ok,
+                                   uint8_t* sums) {
+    std::lock_guard<std::mutex> g(fctx().mu);
+    if (!sums) return fail(ZKMI_ERR_INVALID, "fflonk_aggregate_trace_dev: null argument");
+    return aggregate_entry("fflonk_aggregate_trace_dev", vk_handle, proofs, publics, n_signals, n, seed, codes, ok, sums);
+}
+
+int zkmi_fflonk_aggregate_phase_ms(double* lane_reduce_tail) {
+    std::lock_guard<std::mutex> g(fctx().mu);
+    return fctx().phase_ms("fflonk_aggregate_phase_ms", lane_reduce_tail);
 }
 
 int zkmi_fflonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public) {

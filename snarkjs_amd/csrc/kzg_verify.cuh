@@ -134,6 +134,13 @@ template <class C> ZK_DEV bool xyzz_to_affine(const XYZZ<Fp<C>>& p, Fp<C>& x, Fp
     return true;
 }
 
+// The two G1 points a per-proof check ends in, e(-P, T0) e(Q, T1) == 1 with T0, T1 fixed per key, as the aggregated check takes them over
+// (kzg_aggregate.cuh): affine, Montgomery; *_fin off for the point at infinity.
+template <class C> struct KzgPair {
+    Fp<C> px, py, qx, qy;
+    bool p_fin, q_fin;
+};
+
 // ---- per verifying key: the generators to Montgomery form (g1: x, y), the line tables of the G2 generator and of X_2, omega = Fr.w[power]
 // (passed in Montgomery form), 1/n for n = 2^power, whether X_2 is the point at infinity. True when X_2 is not on its curve. One lane, once.
 template <class C>

@@ -285,6 +285,81 @@ template <class C> ZK_PAIR_OP Fp12<C> final_exp(const Fp12<C>& f, const PairingC
     return r;
 }
 
+// ---- the final exponentiation by a chain of powers of x (used by the aggregated check of kzg_aggregate.cuh only) ------------------
+// |x| from the loop scalar: BN254 x = ((6x + 2) - 2)/6 (positive), BLS12-381 x = -|x| with |x| the loop scalar itself.
+template <class C> ZK_HD constexpr uint64_t curve_x_abs() {
+    if constexpr (PairingCfg<C>::BN_END)
+        return (uint64_t)(((((unsigned __int128)PairingCfg<C>::LOOP_HI) << 64 | PairingCfg<C>::LOOP_LO) - 2) / 6);
+    else
+        return PairingCfg<C>::LOOP_LO;
+}
+// Squaring in the cyclotomic subgroup (Granger-Scott): a^(p^6 + 1) = 1 is assumed. With Fq4 = Fq2[s]/(s^2 - xi) the element splits into three
+// Fq4 pairs (c0.c0, c1.c1), (c1.c0, c0.c2), (c0.c1, c1.c2); each is squared (3 Fq2 squarings) and combined as 3 t -+ 2 a: 9 Fq2 squarings.
+template <class C> ZK_DEV void f4_sqr(const Fp2<C>& a, const Fp2<C>& b, Fp2<C>& c0, Fp2<C>& c1) {
+    const Fp2<C> t0 = f_sqr(a), t1 = f_sqr(b);
+    c0 = f_add(f2_mul_xi(t1), t0);
+    c1 = f_sub(f_sub(f_sqr(f_add(a, b)), t0), t1);
+}
+template <class C> ZK_PAIR_OP Fp12<C> f12_cyclo_sqr(const Fp12<C>& a) {
+    Fp2<C> t0, t1, t2, t3, t4, t5;
+    f4_sqr(a.c0.c0, a.c1.c1, t0, t1);
+    f4_sqr(a.c1.c0, a.c0.c2, t2, t3);
+    f4_sqr(a.c0.c1, a.c1.c2, t4, t5);
+    const Fp2<C> t5x = f2_mul_xi(t5);
+    Fp12<C> r;
+    r.c0.c0 = f_add(f_dbl(f_sub(t0, a.c0.c0)), t0);
+    r.c1.c1 = f_add(f_dbl(f_add(t1, a.c1.c1)), t1);
+    r.c0.c1 = f_add(f_dbl(f_sub(t2, a.c0.c1)), t2);
+    r.c1.c2 = f_add(f_dbl(f_add(t3, a.c1.c2)), t3);
+    r.c1.c0 = f_add(f_dbl(f_add(t5x, a.c1.c0)), t5x);
+    r.c0.c2 = f_add(f_dbl(f_sub(t4, a.c0.c2)), t4);
+    return r;
+}
+// a^|x| for a in the cyclotomic subgroup: MSB-first square-and-multiply over the constant bits of |x|
+template <class C> ZK_PAIR_OP Fp12<C> f12_cyclo_pow_x(const Fp12<C>& a) {
+    constexpr uint64_t X = curve_x_abs<C>();
+    Fp12<C> r = a;
+    bool top = false;
+    for (int i = 63; i >= 0; i--) {
+        const bool bit = (X >> i) & 1;
+        if (top) {
+            r = f12_cyclo_sqr(r);
+            if (bit) r = f12_mul(r, a);
+        }
+        top = top || bit;
+    }
+    return r;
+}
+// final_exp(f)^k for a fixed k coprime to r, so "is one" agrees with final_exp on every f (both give 0 for f = 0):
+//   BN254      k = 2x(6x^2 + 3x + 1): the hard part is t^(l0 + l1 p + l2 p^2 + l3 p^3) with l0 = 12x^3 + 12x^2 + 6x + 1, l1 = 12x^3 + 6x^2 + 4x,
+//              l2 = 12x^3 + 6x^2 + 6x, l3 = 12x^3 + 6x^2 + 4x - 1 (Fuentes-Castaneda, Knapp, Rodriguez-Henriquez, SAC 2011): three powers of x.
+//   BLS12-381  k = 3: the hard part is t^((x - 1)^2 (x + p)(x^2 + p^2 - 1) + 3) (Hayashida, Hayasaka, Teruya 2020); x < 0, so a power of x is
+//              the conjugate (the inverse, in the cyclotomic subgroup) of the power of |x|: five powers of |x|.
+template <class C> ZK_PAIR_OP Fp12<C> final_exp_chain(const Fp12<C>& f, const PairingConsts<C>* K) {
+    Fp12<C> t = f12_mul(f12_conj(f), f12_inv(f));            // ^(p^6 - 1)
+    t = f12_mul(f12_frob(t, K->g2, false), t);               // ^(p^2 + 1)
+    if constexpr (PairingCfg<C>::BN_END) {
+        const Fp12<C> fx = f12_cyclo_pow_x(t), f2x = f12_cyclo_sqr(fx);
+        const Fp12<C> f6x = f12_mul(f12_cyclo_sqr(f2x), f2x);
+        const Fp12<C> f6x2 = f12_cyclo_pow_x(f6x);
+        const Fp12<C> f12x3 = f12_cyclo_pow_x(f12_cyclo_sqr(f6x2));
+        const Fp12<C> a = f12_mul(f12_mul(f12x3, f6x2), f6x);                   // t^(12x^3 + 6x^2 + 6x) = t^l2
+        const Fp12<C> b = f12_mul(a, f12_conj(f2x));                            // t^l1
+        Fp12<C> r = f12_mul(f12_mul(a, f6x2), t);                               // t^l0
+        r = f12_mul(r, f12_frob(b, K->g1, true));
+        r = f12_mul(r, f12_frob(a, K->g2, false));
+        return f12_mul(r, f12_frob(f12_frob(f12_mul(b, f12_conj(t)), K->g2, false), K->g1, true));
+    } else {
+        const Fp12<C> tc = f12_conj(t);
+        const Fp12<C> a = f12_mul(f12_conj(f12_cyclo_pow_x(t)), tc);            // t^(x - 1)
+        const Fp12<C> b = f12_mul(f12_conj(f12_cyclo_pow_x(a)), f12_conj(a));   // t^((x - 1)^2)
+        const Fp12<C> c = f12_mul(f12_conj(f12_cyclo_pow_x(b)), f12_frob(b, K->g1, true));      // ^(x + p)
+        const Fp12<C> cx2 = f12_cyclo_pow_x(f12_cyclo_pow_x(c));                // ^(x^2): two conjugations cancel
+        const Fp12<C> d = f12_mul(f12_mul(cx2, f12_frob(c, K->g2, false)), f12_conj(c));        // ^(x^2 + p^2 - 1)
+        return f12_mul(d, f12_mul(f12_cyclo_sqr(t), t));                        // * t^3
+    }
+}
+
 // ---- point input in the reference's object form (fromObject): (x, y, z) standard form, little-endian --------------------------
 // z = 0: infinity (returned all-zero, flag set); z = 1: affine; otherwise Jacobian (x/z^2, y/z^3). Values >= p are reduced (the
 // Montgomery conversion of a value < R is exact), as F.fromObject reduces.

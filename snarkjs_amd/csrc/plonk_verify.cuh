@@ -77,7 +77,10 @@ template <class C> ZK_PAIR_OP void plonk_vk_prepare(const uint32_t* g1_xyz, cons
 // proof record: A B C Z T1 T2 T3 Wxi Wxiw as (x, y, z) (27 Fq) | eval_a eval_b eval_c eval_s1 eval_s2 eval_zw (8 words each), standard form;
 // pubs: vk.n_public x 8 words. tr (may be null) receives the intermediate values of a proof that passes the input checks.
 template <class C> constexpr int plonk_record_words() { return 27 * C::N + 48; }
-template <class C> ZK_PAIR_OP int plonk_verify_one(const uint32_t* rec, const uint32_t* pubs, const PlonkVkView<C>& V, const PairingConsts<C>* K, PlonkTrace<C>* tr) {
+// With AGG the check stops before the pairing and hands over its two G1 points instead (the aggregated check, kzg_aggregate.cuh); the code is then
+// PLONKV_VALID for "the input checks passed" (KzgPair: kzg_verify.cuh). Without it (the default: the per-proof kernels) the function is what it was.
+template <class C, bool AGG = false>
+ZK_PAIR_OP int plonk_verify_one(const uint32_t* rec, const uint32_t* pubs, const PlonkVkView<C>& V, const PairingConsts<C>* K, PlonkTrace<C>* tr, KzgPair<C>* pair = nullptr) {
     using Fr = typename PairingCfg<C>::Fr;
     using S = Fp<Fr>;
     constexpr int N = C::N;
@@ -197,14 +200,19 @@ template <class C> ZK_PAIR_OP int plonk_verify_one(const uint32_t* rec, const ui
         const Fp<C> p[4] = {fp_from_mont(ax), fp_from_mont(ay), fp_from_mont(bx), fp_from_mont(by)};
         for (int i = 0; i < N; i++) { tr->a1[i] = p[0].l[i]; tr->a1[N + i] = p[1].l[i]; tr->b1[i] = p[2].l[i]; tr->b1[N + i] = p[3].l[i]; }
     }
-    // e(-A1, X_2) e(B1, [1]_2) == 1 (:405-421); pairs are passed as (-px, py)
-    const FixedPair<C> f0{V.tab_x2, fp_neg(ax), fp_neg(ay), a_fin && !vk.x2_inf};
-    const FixedPair<C> f1{V.tab_g2, fp_neg(bx), by, b_fin};
-    Affine<Fp2<C>> none;
-    f_set_zero(none.x);
-    f_set_zero(none.y);
-    const Fp12<C> f = miller_multi(none, ax, ay, false, f0, f1, K);
-    return f12_is_one(final_exp(f, K)) ? PLONKV_VALID : PLONKV_INVALID;
+    if constexpr (AGG) {
+        *pair = KzgPair<C>{ax, ay, bx, by, a_fin, b_fin};
+        return PLONKV_VALID;
+    } else {
+        // e(-A1, X_2) e(B1, [1]_2) == 1 (:405-421); pairs are passed as (-px, py)
+        const FixedPair<C> f0{V.tab_x2, fp_neg(ax), fp_neg(ay), a_fin && !vk.x2_inf};
+        const FixedPair<C> f1{V.tab_g2, fp_neg(bx), by, b_fin};
+        Affine<Fp2<C>> none;
+        f_set_zero(none.x);
+        f_set_zero(none.y);
+        const Fp12<C> f = miller_multi(none, ax, ay, false, f0, f1, K);
+        return f12_is_one(final_exp(f, K)) ? PLONKV_VALID : PLONKV_INVALID;
+    }
 }
 
 }  // namespace zkmi

@@ -5,11 +5,13 @@
 // Per proof (one lane each): plonk_verify_one — input checks, the Keccak-256 transcript, the Fr part, B1 by one 18-base Straus sum, A1, the
 // two-table Miller loop, the final exponentiation.
 //
+// The aggregated check of a whole batch (k_plonk_agg_lane here, then the reduction and the tail of aggregate_host.hpp): kzg_aggregate.cuh.
+//
 // Isolation from the provers and the other verifiers, and the one coupling through hipFree that remains: verify_host.hpp. This verifier's
 // context is pctx().
 #include <stddef.h>
 #include <string.h>
-#include "verify_host.hpp"
+#include "aggregate_host.hpp"
 #include "plonk_verify.cuh"
 
 namespace zkmi {
@@ -30,13 +32,23 @@ template <class C> __global__ void __launch_bounds__(VERIFY_BLOCK) k_plonk_verif
     out[i] = (int8_t)plonk_verify_one(recs + i * plonk_record_words<C>(), pubs + i * 8 * V.vk->n_public, V, K, tr);
 }
 
+// The lane phase of the aggregated check (kzg_aggregate.cuh): plonk_verify_one up to its two points, then r_i times the lane's pair; the block's 64 pairs are added
+// in LDS and leave as one (aggregate_host.hpp agg_lane).
+template <class C> __global__ void __launch_bounds__(VERIFY_BLOCK) k_plonk_agg_lane(const uint32_t* recs, const uint32_t* pubs, uint64_t n, PlonkVkView<C> V,
+                                                                                           const PairingConsts<C>* K, AggSeed seed, int8_t* out, AggPair<C>* parts) {
+    __shared__ AggPair<C> sh[VERIFY_BLOCK];
+    agg_lane<C>(sh, n, seed, out, parts, [&](uint64_t i, KzgPair<C>* pr) {
+        return plonk_verify_one<C, true>(recs + i * plonk_record_words<C>(), pubs + i * 8 * V.vk->n_public, V, K, (PlonkTrace<C>*)nullptr, pr);
+    });
+}
+
 struct PlonkVkEntry {
     int curve = 0;
     uint32_t n_public = 0;
     void* blocks[2] = {nullptr, nullptr};                  // PlonkVk | the line tables of X_2 and of the G2 generator
 };
-VerifyCtx<PlonkVkEntry>& pctx() {
-    static VerifyCtx<PlonkVkEntry> v;
+KzgVerifyCtx<PlonkVkEntry>& pctx() {
+    static KzgVerifyCtx<PlonkVkEntry> v;
     return v;
 }
 
@@ -101,6 +113,40 @@ int verify_entry(const char* who, uint64_t vk_handle, const uint8_t* proofs, con
     return verify_batch<Bls12381Fq>(e, proofs, publics, n, verdicts, trace_out);
 }
 
+template <class C> int aggregate_batch(const PlonkVkEntry& e, const uint8_t* proofs, const uint8_t* publics, size_t n, const uint8_t* seed, int8_t* codes, int* ok, uint8_t* sums) {
+    auto& v = pctx();
+    const PairingConsts<C>* K;
+    ZK_TRY(v.consts<C>(&K));
+    const Line<C>* tabs = (const Line<C>*)e.blocks[1];
+    const PlonkVkView<C> V{(const PlonkVk<C>*)e.blocks[0], tabs, tabs + miller_lines<C>()};
+    AggSeed sd;
+    memcpy(sd.w, seed, 32);
+    const uint32_t* x2_inf = (const uint32_t*)((const uint8_t*)e.blocks[0] + offsetof(PlonkVk<C>, x2_inf));
+    return run_aggregate<C>(v, proofs, n * 4 * plonk_record_words<C>(), publics, n * e.n_public * 32, n, codes, ok, sums, tabs, tabs + miller_lines<C>(), x2_inf, 1, K,
+                                   [&](unsigned blocks, AggPair<C>* parts) {
+        hipLaunchKernelGGL(k_plonk_agg_lane<C>, dim3(blocks), dim3(VERIFY_BLOCK), 0, v.stream, (const uint32_t*)v.in_a.p, (const uint32_t*)v.in_b.p, (uint64_t)n, V, K, sd,
+                           (int8_t*)v.out.p, parts);
+    });
+}
+
+// the aggregated entry: the same refusals as verify_entry; an empty batch is ok; sums (may be null) is zeroed first
+int aggregate_entry(const char* who, uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t* seed, int8_t* codes, int* ok,
+                    uint8_t* sums) {
+    ZK_TRY(pctx().begin());
+    const PlonkVkEntry* found = pctx().find(vk_handle, who);
+    if (!found) return ZKMI_ERR_INVALID;
+    const PlonkVkEntry& e = *found;
+    if (n_signals != e.n_public) return fail(ZKMI_ERR_INVALID, "Invalid number of public inputs");
+    if (!seed || !ok) return fail(ZKMI_ERR_INVALID, std::string(who) + ": null argument");
+    if (sums) memset(sums, 0, e.curve == ZKMI_CURVE_BN128 ? 128 : 192);
+    *ok = 1;
+    if (n == 0) return ZKMI_OK;
+    *ok = 0;
+    if (!proofs || !codes || (n_signals && !publics)) return fail(ZKMI_ERR_INVALID, std::string(who) + ": null argument");
+    if (e.curve == ZKMI_CURVE_BN128) return aggregate_batch<Bn254Fq>(e, proofs, publics, n, seed, codes, ok, sums);
+    return aggregate_batch<Bls12381Fq>(e, proofs, publics, n, seed, codes, ok, sums);
+}
+
 }  // namespace
 }  // namespace zkmi
 
@@ -129,6 +175,23 @@ int zkmi_plonk_verify_trace_dev(uint64_t vk_handle, const uint8_t* proof, const 
     if (!out) return fail(ZKMI_ERR_INVALID, "plonk_verify_trace_dev: null argument");
     int8_t verdict = 0;
     return verify_entry("plonk_verify_trace_dev", vk_handle, proof, publics, n_signals, 1, &verdict, out);
+}
+
+int zkmi_plonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes, int* ok) {
+    std::lock_guard<std::mutex> g(pctx().mu);
+    return aggregate_entry("plonk_verify_aggregate", vk_handle, proofs, publics, n_signals, n, seed, codes, ok, nullptr);
+}
+
+int zkmi_plonk_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes, int* ok,
+                                   uint8_t* sums) {
+    std::lock_guard<std::mutex> g(pctx().mu);
+    if (!sums) return fail(ZKMI_ERR_INVALID, "plonk_aggregate_trace_dev: null argument");
+    return aggregate_entry("plonk_aggregate_trace_dev", vk_handle, proofs, publics, n_signals, n, seed, codes, ok, sums);
+}
+
+int zkmi_plonk_aggregate_phase_ms(double* lane_reduce_tail) {
+    std::lock_guard<std::mutex> g(pctx().mu);
+    return pctx().phase_ms("plonk_aggregate_phase_ms", lane_reduce_tail);
 }
 
 int zkmi_plonk_vk_info(uint64_t vk_handle, int* curve, uint32_t* n_public) {

@@ -1,7 +1,8 @@
 """Batch FFLONK verification on the device: snarkjs.fflonk.verify (src/fflonk_verify.js:28-137) for many proofs against one key. BN254 only:
 the reference's fflonk.setup / fflonk.prove do not work on BLS12-381, so a BLS12-381 key is refused.
 
-One verdict per proof with the reference's per-proof semantics (not a probabilistic batch check). Codes, in the order the reference tests
+One verdict per proof with the reference's per-proof semantics; verify_all / verify_many_fast add the probabilistic check of a whole batch by
+one pairing. Codes, in the order the reference tests
 (which differs from PLONK's: the count comes first): -3 a wrong number of public signals ("Number of public signals does not match with vk"),
 -2 a commitment or the key's C0 not on the curve ("Proof commitments are not valid"), -1 a public input not in [0, r) ("Public inputs are not
 valid."), 0 pairing check failed ("Invalid Proof", logged with warn), 1 valid ("PROOF VERIFIED SUCCESSFULLY"). -4 ("Proof evaluations are not
@@ -78,6 +79,25 @@ class VerifyingKey:
 
     def verify_many(self, public_signals_list, proofs):
         return [c == VALID for c in self.verify_codes(public_signals_list, proofs)]
+
+    def verify_all_raw(self, proofs_u8, publics_u8, n_signals=None, n=None, seed=None):
+        """(ok, codes) of packed records (the layouts of verify_raw) by the aggregated check: ONE pairing check for the batch. ok is True when
+        every proof is valid, and False when one is not except with probability about 2^-127 over the 32-byte seed (drawn from the OS unless
+        given; whoever made the proofs must not know it). codes[i]: proof i's input-check code (-2 / -1), or 1: it entered the check."""
+        return _vc.verify_all_raw(self, zkmi.lib().zkmi_fflonk_verify_aggregate, self.record_bytes, proofs_u8, publics_u8, n_signals, n, self.n_public, seed)
+
+    def verify_all(self, public_signals_list, proofs, seed=None):
+        """are all of these valid? One pairing check for the whole batch (verify_all_raw); an empty batch is. Equals all(verify_many(...))
+        except with probability about 2^-127 over the seed."""
+        return _vc.verify_all(self, public_signals_list, proofs, seed, MESSAGES[BAD_COUNT])
+
+    def verify_many_fast(self, public_signals_list, proofs, seed=None):
+        """verify_many for mostly honest traffic: [True, ...] when the aggregated check passes, else the answer of verify_many"""
+        return _vc.verify_many_fast(self, public_signals_list, proofs, seed, MESSAGES[BAD_COUNT])
+
+    def aggregate_trace(self, public_signals_list, proofs, seed):
+        """zkmi_fflonk_aggregate_trace_dev: (ok, codes, S_P, S_Q), a sum as (x, y) or None"""
+        return _vc.aggregate_trace(self, zkmi.lib().zkmi_fflonk_aggregate_trace_dev, public_signals_list, proofs, seed)
 
     def trace(self, public_signals, proof):
         """zkmi_fflonk_verify_trace_dev for one proof: dict of beta gamma xi alpha y r0 r1 r2 (ints) and A1, B1 ((x, y) or None)"""

@@ -11,7 +11,7 @@
 // Where the reference throws — a wrong count and no logger — this returns false. Calls that arrive while a batch of the same key is on the device join
 // the next batch; keys stay resident per vk content until uninstallFused.
 "use strict";
-const { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, pack, refusedCount, makeVerifier: makeVerifierOf } = require("./verify_common.js");
+const { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, pack, refusedCount, verifyAll, makeVerifier: makeVerifierOf } = require("./verify_common.js");
 
 const BN128 = CURVES.bn128;
 // Fr.w[power] of BN254 is Fr.w[28]^(2^(28 - power)); Fr.w[28] = 5^((r - 1) / 2^28) (ffjavascript: the first non-residue is 5)
@@ -67,6 +67,12 @@ class VerifyingKey {
     }
     async verifyMany(publicSignalsList, proofs) {
         return (await this.verifyCodes(publicSignalsList, proofs)).map((v) => v === 1);
+    }
+    // are all of these valid? One pairing check for the whole batch; equals verifyMany(...).every(Boolean) except with probability about 2^-127 over
+    // the seed ({ seed }: 32 bytes, drawn from the OS unless given)
+    async verifyAll(publicSignalsList, proofs, options) {
+        const A = loadAddon();
+        return verifyAll(this, A.fflonkVerifyAggregateAsync, A.fflonkVerifyAsync, MESSAGES["-3"], publicSignalsList, proofs, options);
     }
     release() {
         if (this.handle) { loadAddon().fflonkVkRelease(this.handle); this.handle = 0; }

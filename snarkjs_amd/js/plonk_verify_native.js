@@ -9,7 +9,7 @@
 // error). Where the reference throws — a bad commitment and no logger — this returns false. Calls that arrive while a batch of the same key is on the
 // device join the next batch; keys stay resident per vk content until uninstallFused.
 "use strict";
-const { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, onCurve, pack, refusedCount, makeVerifier: makeVerifierOf } = require("./verify_common.js");
+const { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, onCurve, pack, refusedCount, verifyAll, makeVerifier: makeVerifierOf } = require("./verify_common.js");
 
 const MESSAGES = { 1: "OK!", 0: "Invalid Proof", "-1": "Public inputs are not valid.", "-2": "Proof commitments are not valid.", "-3": "Invalid number of public inputs" };
 const KEY_POINTS = ["Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3"];
@@ -55,6 +55,12 @@ class VerifyingKey {
     }
     async verifyMany(publicSignalsList, proofs) {
         return (await this.verifyCodes(publicSignalsList, proofs)).map((v) => v === 1);
+    }
+    // are all of these valid? One pairing check for the whole batch; equals verifyMany(...).every(Boolean) except with probability about 2^-127 over
+    // the seed ({ seed }: 32 bytes, drawn from the OS unless given)
+    async verifyAll(publicSignalsList, proofs, options) {
+        const A = loadAddon();
+        return verifyAll(this, A.plonkVerifyAggregateAsync, A.plonkVerifyAsync, MESSAGES["-3"], publicSignalsList, proofs, options);
     }
     release() {
         if (this.handle) { loadAddon().plonkVkRelease(this.handle); this.handle = 0; }

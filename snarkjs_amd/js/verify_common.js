@@ -78,6 +78,28 @@ async function refusedCount(call, message) {
     if (!refused) throw new Error("a wrong number of public signals was not refused");
 }
 
+// the aggregated check of a PLONK / FFLONK key: "are all of these valid?" by one pairing check for the batch (include/zkmi.h zkmi_*_verify_aggregate).
+// aggregateAsync is the addon's plonkVerifyAggregateAsync / fflonkVerifyAggregateAsync, verifyAsync its per-proof call (a wrong number of signals is
+// left to it to refuse, as in verifyCodes). options.seed: 32 bytes the maker of the proofs could not predict; drawn from the OS unless given.
+async function verifyAll(key, aggregateAsync, verifyAsync, countMessage, publicSignalsList, proofs, options) {
+    if (!proofs.length) {
+        if (publicSignalsList.length) throw new Error("one publicSignals list per proof");
+        return true;
+    }
+    const { recs, pubs, nSig, pre } = key.pack(publicSignalsList, proofs);
+    if (nSig !== key.nPublic) {
+        await refusedCount(() => verifyAsync(key.handle, recs, pubs, nSig, proofs.length), countMessage);
+        return false;
+    }
+    if (pre.some((v) => v !== null)) return false;
+    let seed = options && options.seed;
+    if (seed === undefined || seed === null) seed = require("crypto").randomBytes(32);
+    seed = Uint8Array.from(seed);
+    if (seed.length !== 32) throw new Error("the seed of an aggregated check is 32 bytes");
+    const out = await aggregateAsync(key.handle, recs, pubs, nSig, proofs.length, seed);
+    return out[proofs.length] === 1;
+}
+
 // hooks: start (the line logged first, or none), log(logger, code) (the verdict's lines), guard(key, nSig) (may throw before a call is queued)
 function makeVerifier(VerifyingKey, hooks) {
     return function (snarkjs, options) {
@@ -122,4 +144,4 @@ function makeVerifier(VerifyingKey, hooks) {
     };
 }
 
-module.exports = { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, onCurve, pack, refusedCount, makeVerifier };
+module.exports = { CURVES, loadAddon, big, putLE, mod, g1Bytes, g2Bytes, frBytes, onCurve, pack, refusedCount, verifyAll, makeVerifier };

@@ -156,6 +156,13 @@ static int job_run(job_t* j) {
     case 8: return zkmi_groth16_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 9: return zkmi_plonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 10: return zkmi_fflonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
+    case 11: case 12: {                    /* the aggregated check: n code bytes, then the "all valid" byte */
+        int ok = 0;
+        const int rc = (j->kind == 11 ? zkmi_plonk_verify_aggregate : zkmi_fflonk_verify_aggregate)((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb,
+                                                                                                  (size_t)j->n, j->first, (int8_t*)j->o0, &ok);
+        j->o0[(size_t)j->n] = (uint8_t)(ok ? 1 : 0);
+        return rc;
+    }
     default: {
         /* the round drivers of plonk.prove / fflonk.prove (js/plonk_native.js: proveAsync): the call that makes the host WAIT — the commitments of a
          * round, or the queued work before a read-back — runs here on a pool thread, in the pipeline slot of the proof it belongs to */
@@ -1004,9 +1011,13 @@ static size_t fflonk_record_bytes(int curve) { return 12 * (curve == ZKMI_CURVE_
  * the size of the handle's own curve; Groth16 passes NULL and leaves the record length unchecked. */
 static napi_value verify_async_common(napi_env env, napi_callback_info info, int kind, const char* name, int (*vk_info)(uint64_t, int*, uint32_t*),
                                       size_t (*record_bytes)(int)) {
-    ARGS(5);
+    const bool agg = kind == 11 || kind == 12;                      /* a sixth argument, the 32-byte seed; the result has one byte more */
+    size_t argc = 6; napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < (agg ? 6u : 5u)) { napi_throw_type_error(env, NULL, "zkmi: too few arguments"); return NULL; }
     double h, ns, n;
-    pages_t pr, pu;
+    pages_t pr, pu, sd;
+    if (agg && (get_pages(env, argv[5], &sd) || sd.n != 1 || sd.len[0] != 32)) BAD_ARG();
     if (get_f64(env, argv[0], &h) || get_pages(env, argv[1], &pr) || get_pages(env, argv[2], &pu) || get_f64(env, argv[3], &ns) || get_f64(env, argv[4], &n)) BAD_ARG();
     if (n < 1 || ns < 0 || pr.n != 1 || pu.n > 1 || (pu.n == 1 && pu.len[0] != (size_t)n * (size_t)ns * 32) || (pu.n == 0 && ns != 0)) BAD_ARG();
     if (record_bytes) {
@@ -1016,11 +1027,12 @@ static napi_value verify_async_common(napi_env env, napi_callback_info info, int
         if (pr.len[0] != (size_t)n * record_bytes(curve)) BAD_ARG();
     }
     uint8_t* out;
-    napi_value res = new_u8(env, (size_t)n, &out);
+    napi_value res = new_u8(env, (size_t)n + (agg ? 1 : 0), &out);
     if (!res) BAD_ARG();
     job_t* j = (job_t*)calloc(1, sizeof *j);
     if (!j) BAD_ARG();
     j->kind = kind; j->key = h; j->a = pr; j->b = pu; j->sb = ns; j->n = n; j->o0 = out;
+    if (agg) memcpy(j->first, sd.ptr[0], 32);
     if (pu.n == 1 && pu.len[0] == 0) j->b.n = 0;
     return job_queue(env, j, name, argv, 5, res);
 }
@@ -1066,6 +1078,10 @@ static napi_value js_plonk_vk_load(napi_env env, napi_callback_info info) {
 }
 static napi_value js_plonk_verify_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 9, "zkmi.plonkVerify", zkmi_plonk_vk_info, plonk_record_bytes); }
 static napi_value js_plonk_vk_release(napi_env env, napi_callback_info info) { return vk_release_common(env, info, zkmi_plonk_vk_release); }
+/* plonkVerifyAggregateAsync / fflonkVerifyAggregateAsync(handle, proofs, publics, nSignals, n, seed32) -> Promise<Uint8Array(n + 1)>: the aggregated check
+ * (include/zkmi.h zkmi_*_verify_aggregate) on a libuv pool thread: n code bytes (int8: the input checks' code or 1), then one byte: 1 = all valid. */
+static napi_value js_plonk_verify_aggregate_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 11, "zkmi.plonkVerifyAggregate", zkmi_plonk_vk_info, plonk_record_bytes); }
+static napi_value js_fflonk_verify_aggregate_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 12, "zkmi.fflonkVerifyAggregate", zkmi_fflonk_vk_info, fflonk_record_bytes); }
 
 /* ---- FFLONK verification (src/fflonk_verify.js:28-137; include/zkmi.h zkmi_fflonk_vk_load / _verify_batch / _vk_info / _vk_release), BN254 only ---
  * fflonkVkLoad(curve, c0Xyz, x2Xyz, consts (k1 k2 w3 w4 w8 wr), power, nPublic) -> handle.
@@ -1117,6 +1133,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"peerCopy", js_peer_copy}, {"peerCopyAsync", js_peer_copy_async}, {"peerFence", js_peer_fence}, {"groth16Reset", js_groth16_reset}, {"groth16KeyCurve", js_groth16_key_curve},
         {"groth16VkLoad", js_groth16_vk_load}, {"groth16VerifyAsync", js_groth16_verify_async}, {"groth16VkRelease", js_groth16_vk_release},
         {"plonkVkLoad", js_plonk_vk_load}, {"plonkVerifyAsync", js_plonk_verify_async}, {"plonkVkRelease", js_plonk_vk_release},
+        {"plonkVerifyAggregateAsync", js_plonk_verify_aggregate_async}, {"fflonkVerifyAggregateAsync", js_fflonk_verify_aggregate_async},
         {"fflonkVkLoad", js_fflonk_vk_load}, {"fflonkVerifyAsync", js_fflonk_verify_async}, {"fflonkVkInfo", js_fflonk_vk_info}, {"fflonkVkRelease", js_fflonk_vk_release},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -192,8 +192,58 @@ def main_fflonk():
     print(json.dumps(out))
 
 
+def main_aggregate(protocol):
+    """--aggregate: the aggregated check (verify_all_raw) beside the per-proof path (verify_raw) of the same key, in one run on one device, on the same
+    `VERIFYBENCH_DISTINCT` (256) distinct device proofs tiled to the batch (VERIFYBENCH_SIZES, default 4096,65536,262144): packed calls per
+    second both ways, the per-proof kernel's HIP-event time, and the aggregated path's split into lane phase, reduction and tail."""
+    import numpy as np
+    import fflonk_verify_vectors as FV
+    import plonk_verify_vectors as PV
+    from snarkjs_amd import fflonk, fflonk_verify, plonk, plonk_verify, zkmi
+    sizes = [int(x) for x in os.environ.get("VERIFYBENCH_SIZES", "4096,65536,262144").split(",")]
+    reps = int(os.environ.get("VERIFYBENCH_REPS", "3"))
+    n_distinct = max(64, int(os.environ.get("VERIFYBENCH_DISTINCT", "256")))
+    out = {"what": protocol + " aggregated batch verify vs per-proof verify_raw", "reps": reps, "distinct_proofs": n_distinct, "curves": {}}
+    gd = os.path.join(ROOT, "tests", "golden")
+    L = zkmi.lib()
+    tags = ("plonk_bn128_n2048", "plonk_bls12381_small") if protocol == "plonk" else ("fflonk_bn128_n256",)
+    vec, prover, mod = (PV, plonk, plonk_verify) if protocol == "plonk" else (FV, fflonk, fflonk_verify)
+    for tag in tags:
+        vk, pubs, _ = vec.golden(tag + ".json")
+        res_all = prover.prove_many(open(os.path.join(gd, tag + ".zkey"), "rb").read(), [open(os.path.join(gd, tag + ".wtns"), "rb").read()] * n_distinct)
+        distinct = [r["proof"] for r in res_all]
+        key = mod.VerifyingKey(vk)
+        r1, p1, ns, _ = key.pack([pubs] * n_distinct, distinct)
+        res = {}
+        for n in sizes:
+            tiles = (n + n_distinct - 1) // n_distinct
+            recs, pu = np.tile(r1, tiles)[:n * key.record_bytes], np.tile(p1, tiles)[:n * ns * 32]
+            seed = bytes(range(32))
+            entry = {"verify_raw": rate(lambda: key.verify_raw(recs, pu, ns, n), n, reps)}
+            entry["per_proof_kernel_ms"] = round(getattr(L, "zkmi_%s_verify_last_ms" % protocol)(), 3)
+            entry["verify_all_raw"] = rate(lambda: key.verify_all_raw(recs, pu, ns, n, seed), n, reps)
+            ms = (zkmi.C.c_double * 3)()
+            zkmi.check(getattr(L, "zkmi_%s_aggregate_phase_ms" % protocol)(ms))
+            entry["aggregate_ms"] = {"lane": round(ms[0], 3), "reduce": round(ms[1], 3), "tail": round(ms[2], 3)}
+            entry["lane_vs_per_proof_kernel"] = round(ms[0] / entry["per_proof_kernel_ms"], 3)
+            entry["aggregate_vs_per_proof_rate"] = round(entry["verify_all_raw"]["per_s"] / entry["verify_raw"]["per_s"], 3)
+            ok, codes = key.verify_all_raw(recs, pu, ns, n, seed)
+            assert ok and (codes == 1).all()
+            res[str(n)] = entry
+        key.release()
+        out["curves"][vk.get("curve", "bn128")] = res
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--protocol", choices=["groth16", "plonk", "fflonk"], default="groth16")
-    {"groth16": main, "plonk": main_plonk, "fflonk": main_fflonk}[ap.parse_args().protocol]()
+    ap.add_argument("--aggregate", action="store_true", help="plonk / fflonk: the aggregated check beside the per-proof path")
+    args = ap.parse_args()
+    if args.aggregate:
+        if args.protocol == "groth16":
+            ap.error("--aggregate serves plonk and fflonk")
+        main_aggregate(args.protocol)
+    else:
+        {"groth16": main, "plonk": main_plonk, "fflonk": main_fflonk}[args.protocol]()
