@@ -286,6 +286,14 @@ int zkmi_plonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const
                                 int* ok);
 int zkmi_fflonk_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
                                  int* ok);
+/* The aggregated check of a batch under one Groth16 key: "are ALL of these valid?" by ONE final exponentiation. Records and refusals
+ * as zkmi_groth16_verify_batch (n_signals below nPublic is accepted, above is refused); seed and r_i as above. codes[i] = the input checks' code of
+ * proof i (-1 / -2) or 1: it entered F = prod Miller(-r_i A_i, B_i), S_X = sum r_i vk_x_i, S_C = sum r_i C_i and s = sum r_i; *ok = 1 exactly when
+ * every code is 1 and F e(S_X, gamma) e(S_C, delta) e(alpha, beta)^s reduces to 1. An empty batch is ok. If every per-proof verdict is 1, ok is 1;
+ * if one is not, ok is 0 except with probability about 2^-127 over the seed (proof points in G1 / G2; on BLS12-381 the two sums are multiplied by
+ * the G1 cofactor and the other factors raised to it). */
+int zkmi_groth16_verify_aggregate(uint64_t vk_handle, const uint8_t* proofs_xyz, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                  int* ok);
 /* Multi-GPU proof (BASELINE configs[2]: MSMs sharded across the GPUs of a node). Every rank loads the shard of the
  * key that holds the witness-side bases of the variables [var_lo, var_hi) (sections 5-8) and the H bases [h_lo, h_hi) (section 9);
  * the section pointers of `zkey` are those of the FULL sections, the library slices them. zkmi_groth16_sums_dev runs the device

@@ -71,7 +71,8 @@ int zkmi_groth16_coef_layout(uint64_t zkey_cache_key, uint64_t* out, int n);
  * for tests and debugging: g1_xyz n x 3 Fq, g2_xyz n x 3 Fq2 in the (x, y, z) form of zkmi_groth16_vk_load; out_f12 n x 12 Fq, standard form,
  * the coefficients of w^0..w^11 in Fq[w]/(w^12 - 2s w^6 + s^2 + 1), xi = s + u (oracle/groth16_verify_oracle.py). A point at infinity gives 1. */
 int zkmi_pairing_dev(int curve, const uint8_t* g1_xyz, const uint8_t* g2_xyz, size_t n, uint8_t* out_f12);
-/* Device time of the verification kernel of the last zkmi_groth16_verify_batch, in milliseconds (HIP events on the verifier's stream); -1: none yet. */
+/* Device time of the verification kernel of the last zkmi_groth16_verify_batch, in milliseconds (HIP events on the verifier's stream); -1: none yet.
+ * After an aggregated batch: its three phases together. */
 double zkmi_groth16_verify_last_ms(void);
 /* The intermediate values of the PLONK verifier for ONE proof (inputs as zkmi_plonk_verify_batch with n = 1), so that a wrong verdict can be
  * located: out = beta gamma alpha xi v1 u L1(xi) PI(xi) r0 (9 x 32 bytes, Fr, standard form) | A1.x A1.y B1.x B1.y (n8q bytes each, affine,
@@ -95,6 +96,13 @@ int zkmi_fflonk_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs, c
  * last batch was not an aggregated one). After an aggregated batch zkmi_*_verify_last_ms reports the three together. */
 int zkmi_plonk_aggregate_phase_ms(double* lane_reduce_tail);
 int zkmi_fflonk_aggregate_phase_ms(double* lane_reduce_tail);
+/* zkmi_groth16_verify_aggregate with its intermediate values reported: trace = S_X.x S_X.y S_C.x S_C.y (n8q bytes each, affine, standard form,
+ * before the cofactor multiplication; the point at infinity all-zero) | s = sum r_i (24 bytes, little-endian) | final_exp(F), the plain final
+ * exponentiation of the product of the lanes' Miller values, as 12 Fq in the w-basis of zkmi_pairing_dev: 16 n8q + 24 bytes. */
+int zkmi_groth16_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs_xyz, const uint8_t* publics, uint32_t n_signals, size_t n, const uint8_t seed[32], int8_t* codes,
+                                     int* ok, uint8_t* trace);
+/* lane phase | reduction | tail of the Groth16 verifier's last batch when it was an aggregated one (-1 each otherwise), as above */
+int zkmi_groth16_aggregate_phase_ms(double* lane_reduce_tail);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """What the three batch verifiers (groth16_verify, plonk_verify, fflonk_verify) share on the host: field-element and point encoding, the
 public-signal half of a packed batch, the size checks around a *_verify_batch call, the trace decoder, the aggregated check
-of the two KZG verifiers (verify_all / verify_all_raw / verify_many_fast), the cache behind verify() /
+(verify_all / verify_all_raw / verify_many_fast), the cache behind verify() /
 release_all() (each module passes its own dict) and the zkey header reader of the two vk_from_zkey. Needs no device except root()."""
 import json
 import os
@@ -103,8 +103,9 @@ def new_seed(seed):
 
 
 def verify_all_raw(key, verify_aggregate, rec, proofs_u8, publics_u8, n_signals, n, n_sig_empty, seed, sums=None):
-    """(ok, codes) of packed records by the library's *_verify_aggregate of key's protocol (or, with sums = a uint8 array of 4 n8 bytes, its
-    *_aggregate_trace_dev): ONE pairing check for the batch; codes[i] is proof i's input-check code or 1 (entered the sums)"""
+    """(ok, codes) of packed records by the library's *_verify_aggregate of key's protocol (or, with sums = a uint8 array of the size its
+    *_aggregate_trace_dev reports — 4 n8 bytes for the KZG protocols, 16 n8 + 24 for Groth16 — that call): ONE pairing check for the batch;
+    codes[i] is proof i's input-check code or 1 (entered the sums)"""
     proofs_u8, publics_u8 = zkmi.u8(proofs_u8), zkmi.u8(publics_u8)
     if n is None:
         n = proofs_u8.size // rec
@@ -124,9 +125,9 @@ def verify_all_raw(key, verify_aggregate, rec, proofs_u8, publics_u8, n_signals,
 
 def verify_all(key, public_signals_list, proofs, seed, count_message):
     """are all of these valid? False where a public signal is out of range (caught while packing) or the number of signals is wrong (refused by
-    the device call as a whole, as in verify_codes)"""
+    the device call as a whole, as in verify_codes; count_message None: the protocol accepts fewer signals and pack() raises on more — Groth16)"""
     recs, pubs, n_sig, pre = key.pack(public_signals_list, proofs)
-    if proofs and n_sig != key.n_public:
+    if count_message is not None and proofs and n_sig != key.n_public:
         refused_count(key, recs, pubs, n_sig, len(proofs), count_message)
         return False
     if any(c is not None for c in pre):
@@ -141,16 +142,18 @@ def verify_many_fast(key, public_signals_list, proofs, seed, count_message):
     return key.verify_many(public_signals_list, proofs)
 
 
-def aggregate_trace(key, aggregate_trace_dev, public_signals_list, proofs, seed):
-    """*_aggregate_trace_dev: (ok, codes, S_P, S_Q) with a sum as (x, y) or None for the point at infinity"""
+def aggregate_trace(key, aggregate_trace_dev, public_signals_list, proofs, seed, more_bytes=0):
+    """*_aggregate_trace_dev: (ok, codes, S_P, S_Q) with a sum as (x, y) or None for the point at infinity; with more_bytes, the bytes the
+    protocol's report holds after its two sums come fifth"""
     recs, pubs, n_sig, pre = key.pack(public_signals_list, proofs)
     if any(c is not None for c in pre):
         raise ValueError("a public signal is outside [0, r)")
     n8 = key.n8
-    sums = np.zeros(4 * n8, np.uint8)
-    ok, codes = verify_all_raw(key, aggregate_trace_dev, key.record_bytes, recs, pubs, n_sig, len(proofs), key.n_public, seed, sums)
+    sums = np.zeros(4 * n8 + more_bytes, np.uint8)
+    ok, codes = verify_all_raw(key, aggregate_trace_dev, key.record_bytes, recs, pubs, n_sig, len(proofs), n_sig, seed, sums)
     v = [int.from_bytes(sums[i * n8:(i + 1) * n8].tobytes(), "little") for i in range(4)]
-    return ok, codes, (None if (v[0], v[1]) == (0, 0) else (v[0], v[1])), (None if (v[2], v[3]) == (0, 0) else (v[2], v[3]))
+    res = (ok, codes, (None if (v[0], v[1]) == (0, 0) else (v[0], v[1])), (None if (v[2], v[3]) == (0, 0) else (v[2], v[3])))
+    return res + (sums[4 * n8:].tobytes(),) if more_bytes else res
 
 
 def refused_count(key, recs, pubs, n_sig, n, message):

@@ -7,8 +7,9 @@
 // rules as a per-proof batch; the partial sums live in two further buffers of the context, which only grow. No point arithmetic on the host:
 // the host reads the codes and the tail's one-word verdict.
 //
-// KzgVerifyCtx is VerifyCtx (verify_host.hpp, unchanged and still what the Groth16 verifier uses) plus what an aggregated batch needs: two more
-// events, the buffers of the partial sums and of the tail's report, and which kind of batch ran last.
+// KzgVerifyCtx is VerifyCtx (verify_host.hpp, unchanged) plus what an aggregated batch needs: two more events, the buffers of the partial sums and
+// of the tail's report, and which kind of batch ran last. The Groth16 verifier uses it too, with kernels and records of its own
+// (groth16_verify.hip, groth16_aggregate.cuh).
 #pragma once
 #include <string.h>
 #include "verify_host.hpp"

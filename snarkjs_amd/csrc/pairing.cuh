@@ -403,9 +403,20 @@ template <class C> ZK_DEV bool public_below_r(const uint32_t* s) {
     for (int i = 0; i < 8; i++) (void)__builtin_subc(s[i], Fr::p(i), bw, &bw);
     return bw != 0;
 }
-// proof record: pi_a (3 Fq), pi_b (3 Fq2), pi_c (3 Fq), standard form; publics: n_signals x 8 words
-template <class C> ZK_DEV int groth16_verify_one(const uint32_t* rec, const uint32_t* pubs, uint32_t n_signals, const VkView<C>& vk,
-                                                  const PairingConsts<C>* K) {
+// What a proof that passes the input checks hands to the aggregated check (groth16_aggregate.cuh): its three points and vk_x, affine, Montgomery;
+// *_inf set for the point at infinity (the coordinates are then all-zero).
+template <class C> struct G16Front {
+    Affine<Fp<C>> A, Cp;
+    Affine<Fp2<C>> B;
+    Fp<C> vx, vy;
+    bool a_inf, b_inf, c_inf, x_inf;
+};
+// proof record: pi_a (3 Fq), pi_b (3 Fq2), pi_c (3 Fq), standard form; publics: n_signals x 8 words.
+// With AGG the check stops before the Miller loop and hands over its front half instead (the code is then G16V_VALID for "the input checks
+// passed"). Without it (the default: k_g16_verify) the function is what it was.
+template <class C, bool AGG = false>
+ZK_DEV int groth16_verify_one(const uint32_t* rec, const uint32_t* pubs, uint32_t n_signals, const VkView<C>& vk, const PairingConsts<C>* K,
+                              G16Front<C>* front = nullptr) {
     constexpr int N = C::N;
     for (uint32_t j = 0; j < n_signals; j++)
         if (!public_below_r<C>(pubs + 8 * j)) return G16V_BAD_PUBLIC;
@@ -431,12 +442,17 @@ template <class C> ZK_DEV int groth16_verify_one(const uint32_t* rec, const uint
         vx = fp_mul(acc.X, fp_mul(i, acc.ZZZ));
         vy = fp_mul(acc.Y, fp_mul(i, acc.ZZ));
     }
-    // e(-A, B) e(vk_x, gamma) e(C, delta) e(alpha, beta) == 1; the pairs are passed as (-px, py): -A = (A.x, -A.y)
-    const FixedPair<C> g{vk.tab_gamma, fp_neg(vx), vy, !x_inf && !vk.gamma_inf};
-    const FixedPair<C> d{vk.tab_delta, fp_neg(Cp.x), Cp.y, !c_inf && !vk.delta_inf};
-    Fp12<C> f = miller_multi(B, fp_neg(A.x), fp_neg(A.y), !a_inf && !b_inf, g, d, K);
-    f = f12_mul(f, *vk.mab);
-    return f12_is_one(final_exp(f, K)) ? G16V_VALID : G16V_INVALID;
+    if constexpr (AGG) {
+        *front = G16Front<C>{A, Cp, B, vx, vy, a_inf, b_inf, c_inf, x_inf};
+        return G16V_VALID;
+    } else {
+        // e(-A, B) e(vk_x, gamma) e(C, delta) e(alpha, beta) == 1; the pairs are passed as (-px, py): -A = (A.x, -A.y)
+        const FixedPair<C> g{vk.tab_gamma, fp_neg(vx), vy, !x_inf && !vk.gamma_inf};
+        const FixedPair<C> d{vk.tab_delta, fp_neg(Cp.x), Cp.y, !c_inf && !vk.delta_inf};
+        Fp12<C> f = miller_multi(B, fp_neg(A.x), fp_neg(A.y), !a_inf && !b_inf, g, d, K);
+        f = f12_mul(f, *vk.mab);
+        return f12_is_one(final_exp(f, K)) ? G16V_VALID : G16V_INVALID;
+    }
 }
 
 // Fq12 (tower) -> the oracle's w-basis, 12 Fq coefficients in standard form: c_k = a + b u -> (a - s b) w^k + b w^(k+6)

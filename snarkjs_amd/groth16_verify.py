@@ -1,6 +1,7 @@
 """Batch Groth16 verification on the device: snarkjs.groth16.verify (src/groth16_verify.js:26-87) for many proofs against one key.
 
-One verdict per proof with the reference's per-proof semantics (not a probabilistic batch check). Codes: 1 valid ("OK!"), 0 pairing check
+One verdict per proof with the reference's per-proof semantics; verify_all / verify_many_fast add the probabilistic check of a whole batch by
+one final exponentiation. Codes: 1 valid ("OK!"), 0 pairing check
 failed ("Invalid proof"), -1 a public input not in [0, r) ("Public inputs are not valid."), -2 a proof point not on the curve ("Proof
 commitments are not valid."). The kernels are csrc/groth16_verify.hip; there is no CPU path.
 """
@@ -51,6 +52,33 @@ class VerifyingKey:
 
     def verify_many(self, public_signals_list, proofs):
         return [c == VALID for c in self.verify_codes(public_signals_list, proofs)]
+
+    @property
+    def record_bytes(self):
+        return 12 * self.n8
+
+    def verify_all_raw(self, proofs_u8, publics_u8, n_signals=None, n=None, seed=None):
+        """(ok, codes) of packed records (the layouts of verify_raw) by the aggregated check: one Miller loop per proof, ONE final exponentiation
+        for the batch. ok is True when every proof is valid, and False when one is not except with probability about 2^-127 over the 32-byte
+        seed (drawn from the OS unless given; whoever made the proofs must not know it). codes[i]: proof i's input-check code (-1 / -2), or 1:
+        it entered the check."""
+        return _vc.verify_all_raw(self, zkmi.lib().zkmi_groth16_verify_aggregate, self.record_bytes, proofs_u8, publics_u8, n_signals, n, 0, seed)
+
+    def verify_all(self, public_signals_list, proofs, seed=None):
+        """are all of these valid? One final exponentiation for the whole batch (verify_all_raw); an empty batch is. Equals
+        all(verify_many(...)) except with probability about 2^-127 over the seed."""
+        return _vc.verify_all(self, public_signals_list, proofs, seed, None)
+
+    def verify_many_fast(self, public_signals_list, proofs, seed=None):
+        """verify_many for mostly honest traffic: [True, ...] when the aggregated check passes, else the answer of verify_many"""
+        return _vc.verify_many_fast(self, public_signals_list, proofs, seed, None)
+
+    def aggregate_trace(self, public_signals_list, proofs, seed):
+        """zkmi_groth16_aggregate_trace_dev: (ok, codes, S_X, S_C, s, GT) — a sum as (x, y) or None, s = sum r_i, GT = final_exp of the
+        product of the lanes' Miller values as 12 Fq coefficients in the oracle's w-basis"""
+        n8 = self.n8
+        ok, codes, sx, sc, more = _vc.aggregate_trace(self, zkmi.lib().zkmi_groth16_aggregate_trace_dev, public_signals_list, proofs, seed, 24 + 12 * n8)
+        return ok, codes, sx, sc, int.from_bytes(more[:24], "little"), [int.from_bytes(more[24 + k * n8:24 + (k + 1) * n8], "little") for k in range(12)]
 
     def release(self):
         _vc.release(self, zkmi.lib().zkmi_groth16_vk_release)

@@ -3,12 +3,13 @@
 //   const { VerifyingKey } = require("snarkjs_amd/js/groth16_verify_native.js");
 //   const vk = new VerifyingKey(vkJson, { device: 0 });          // the object zKey.exportVerificationKey writes
 //   const ok = await vk.verifyMany(publicSignalsList, proofs);    // boolean[], one per proof, the reference's per-proof verdicts
+//   const all = await vk.verifyAll(publicSignalsList, proofs);    // boolean: are all of them valid? One final exponentiation for the batch
 //
 // makeVerifier(snarkjs) is what registerAll(snarkjs, { fused: true, verify: true }) puts behind snarkjs.groth16.verify: the reference's signature,
 // return value and logger messages (src/groth16_verify.js:26-87); calls that arrive while a batch of the same key is on the device join the next batch;
 // keys stay resident per vk content until uninstallFused.
 "use strict";
-const { CURVES, loadAddon, g1Bytes, g2Bytes, pack, makeVerifier: makeVerifierOf } = require("./verify_common.js");
+const { CURVES, loadAddon, g1Bytes, g2Bytes, pack, verifyAll, makeVerifier: makeVerifierOf } = require("./verify_common.js");
 
 const MESSAGES = { 1: "OK!", 0: "Invalid proof", "-1": "Public inputs are not valid.", "-2": "Proof commitments are not valid." };
 
@@ -45,6 +46,11 @@ class VerifyingKey {
     }
     async verifyMany(publicSignalsList, proofs) {
         return (await this.verifyCodes(publicSignalsList, proofs)).map((v) => v === 1);
+    }
+    // are all of these valid? One Miller loop per proof and ONE final exponentiation for the batch; equals verifyMany(...).every(Boolean) except with
+    // probability about 2^-127 over the seed ({ seed }: 32 bytes, drawn from the OS unless given)
+    async verifyAll(publicSignalsList, proofs, options) {
+        return verifyAll(this, loadAddon().groth16VerifyAggregateAsync, null, null, publicSignalsList, proofs, options);
     }
     release() {
         if (this.handle) { loadAddon().groth16VkRelease(this.handle); this.handle = 0; }

@@ -78,16 +78,17 @@ async function refusedCount(call, message) {
     if (!refused) throw new Error("a wrong number of public signals was not refused");
 }
 
-// the aggregated check of a PLONK / FFLONK key: "are all of these valid?" by one pairing check for the batch (include/zkmi.h zkmi_*_verify_aggregate).
-// aggregateAsync is the addon's plonkVerifyAggregateAsync / fflonkVerifyAggregateAsync, verifyAsync its per-proof call (a wrong number of signals is
-// left to it to refuse, as in verifyCodes). options.seed: 32 bytes the maker of the proofs could not predict; drawn from the OS unless given.
+// the aggregated check of a key: "are all of these valid?" by one pairing check for the batch (include/zkmi.h zkmi_*_verify_aggregate).
+// aggregateAsync is the addon's *VerifyAggregateAsync, verifyAsync its per-proof call (a wrong number of signals is left to it to refuse, as in
+// verifyCodes; null for Groth16, which accepts fewer signals and whose pack() throws on more). options.seed: 32 bytes the maker of the proofs could
+// not predict; drawn from the OS unless given.
 async function verifyAll(key, aggregateAsync, verifyAsync, countMessage, publicSignalsList, proofs, options) {
     if (!proofs.length) {
         if (publicSignalsList.length) throw new Error("one publicSignals list per proof");
         return true;
     }
     const { recs, pubs, nSig, pre } = key.pack(publicSignalsList, proofs);
-    if (nSig !== key.nPublic) {
+    if (verifyAsync && nSig !== key.nPublic) {
         await refusedCount(() => verifyAsync(key.handle, recs, pubs, nSig, proofs.length), countMessage);
         return false;
     }

@@ -156,10 +156,10 @@ static int job_run(job_t* j) {
     case 8: return zkmi_groth16_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 9: return zkmi_plonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 10: return zkmi_fflonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
-    case 11: case 12: {                    /* the aggregated check: n code bytes, then the "all valid" byte */
+    case 11: case 12: case 13: {           /* the aggregated check: n code bytes, then the "all valid" byte */
         int ok = 0;
-        const int rc = (j->kind == 11 ? zkmi_plonk_verify_aggregate : zkmi_fflonk_verify_aggregate)((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb,
-                                                                                                  (size_t)j->n, j->first, (int8_t*)j->o0, &ok);
+        const int rc = (j->kind == 11 ? zkmi_plonk_verify_aggregate : j->kind == 12 ? zkmi_fflonk_verify_aggregate : zkmi_groth16_verify_aggregate)(
+            (uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, j->first, (int8_t*)j->o0, &ok);
         j->o0[(size_t)j->n] = (uint8_t)(ok ? 1 : 0);
         return rc;
     }
@@ -1011,7 +1011,7 @@ static size_t fflonk_record_bytes(int curve) { return 12 * (curve == ZKMI_CURVE_
  * the size of the handle's own curve; Groth16 passes NULL and leaves the record length unchecked. */
 static napi_value verify_async_common(napi_env env, napi_callback_info info, int kind, const char* name, int (*vk_info)(uint64_t, int*, uint32_t*),
                                       size_t (*record_bytes)(int)) {
-    const bool agg = kind == 11 || kind == 12;                      /* a sixth argument, the 32-byte seed; the result has one byte more */
+    const bool agg = kind >= 11 && kind <= 13;                      /* a sixth argument, the 32-byte seed; the result has one byte more */
     size_t argc = 6; napi_value argv[6];
     NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < (agg ? 6u : 5u)) { napi_throw_type_error(env, NULL, "zkmi: too few arguments"); return NULL; }
@@ -1056,6 +1056,9 @@ static napi_value js_groth16_vk_load(napi_env env, napi_callback_info info) {
     return vk_handle_value(env, rc, h);
 }
 static napi_value js_groth16_verify_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 8, "zkmi.groth16Verify", NULL, NULL); }
+/* groth16VerifyAggregateAsync(handle, proofsXyz, publics, nSignals, n, seed32) -> Promise<Uint8Array(n + 1)>: the aggregated check (include/zkmi.h
+ * zkmi_groth16_verify_aggregate) on a libuv pool thread: n code bytes (int8: the input checks' code or 1), then one byte: 1 = all valid. */
+static napi_value js_groth16_verify_aggregate_async(napi_env env, napi_callback_info info) { return verify_async_common(env, info, 13, "zkmi.groth16VerifyAggregate", NULL, NULL); }
 static napi_value js_groth16_vk_release(napi_env env, napi_callback_info info) { return vk_release_common(env, info, zkmi_groth16_vk_release); }
 
 /* ---- PLONK verification (src/plonk_verify.js:29-123; include/zkmi.h zkmi_plonk_vk_load / _verify_batch / _vk_release) ---------------------------
@@ -1131,7 +1134,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"groth16Finish", js_groth16_finish}, {"joinABCDev", js_join_abc_dev}, {"pointAdd", js_point_add}, {"shmMap", js_shm_map}, {"shmUnlink", js_shm_unlink},
         {"msmTableDev", js_msm_table_dev}, {"msmTableMultiDev", js_msm_table_multi_dev}, {"msmTableMultiDevAsync", js_msm_table_multi_dev_async}, {"msmTableMultiEnqueueDev", js_msm_table_multi_enqueue_dev}, {"msmTableMultiEnqueueMontDev", js_msm_table_multi_enqueue_mont_dev}, {"msmTableMultiCollect", js_msm_table_multi_collect}, {"synchronizeAsync", js_synchronize_async}, {"ipcExport", js_ipc_export}, {"ipcOpen", js_ipc_open}, {"ipcClose", js_ipc_close},
         {"peerCopy", js_peer_copy}, {"peerCopyAsync", js_peer_copy_async}, {"peerFence", js_peer_fence}, {"groth16Reset", js_groth16_reset}, {"groth16KeyCurve", js_groth16_key_curve},
-        {"groth16VkLoad", js_groth16_vk_load}, {"groth16VerifyAsync", js_groth16_verify_async}, {"groth16VkRelease", js_groth16_vk_release},
+        {"groth16VkLoad", js_groth16_vk_load}, {"groth16VerifyAsync", js_groth16_verify_async}, {"groth16VerifyAggregateAsync", js_groth16_verify_aggregate_async}, {"groth16VkRelease", js_groth16_vk_release},
         {"plonkVkLoad", js_plonk_vk_load}, {"plonkVerifyAsync", js_plonk_verify_async}, {"plonkVkRelease", js_plonk_vk_release},
         {"plonkVerifyAggregateAsync", js_plonk_verify_aggregate_async}, {"fflonkVerifyAggregateAsync", js_fflonk_verify_aggregate_async},
         {"fflonkVkLoad", js_fflonk_vk_load}, {"fflonkVerifyAsync", js_fflonk_verify_async}, {"fflonkVkInfo", js_fflonk_vk_info}, {"fflonkVkRelease", js_fflonk_vk_release},

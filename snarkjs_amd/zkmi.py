@@ -39,7 +39,7 @@ SYMBOLS = [
     "zkmi_plonk_vk_load", "zkmi_plonk_verify_batch", "zkmi_plonk_vk_release", "zkmi_plonk_vk_info", "zkmi_plonk_verify_trace_dev", "zkmi_plonk_verify_last_ms",
     "zkmi_fflonk_vk_load", "zkmi_fflonk_verify_batch", "zkmi_fflonk_vk_release", "zkmi_fflonk_vk_info", "zkmi_fflonk_verify_trace_dev", "zkmi_fflonk_verify_last_ms",
     "zkmi_plonk_verify_aggregate", "zkmi_fflonk_verify_aggregate", "zkmi_plonk_aggregate_trace_dev", "zkmi_fflonk_aggregate_trace_dev", "zkmi_plonk_aggregate_phase_ms",
-    "zkmi_fflonk_aggregate_phase_ms",
+    "zkmi_fflonk_aggregate_phase_ms", "zkmi_groth16_verify_aggregate", "zkmi_groth16_aggregate_trace_dev", "zkmi_groth16_aggregate_phase_ms",
 ]
 
 
@@ -243,7 +243,7 @@ def lib():
     L.zkmi_fflonk_verify_trace_dev.argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, u8p]
     L.zkmi_fflonk_verify_last_ms.argtypes = []
     L.zkmi_fflonk_verify_last_ms.restype = C.c_double
-    for proto in ("plonk", "fflonk"):
+    for proto in ("groth16", "plonk", "fflonk"):
         getattr(L, f"zkmi_{proto}_verify_aggregate").argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p, u8p, C.POINTER(C.c_int)]
         getattr(L, f"zkmi_{proto}_aggregate_trace_dev").argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p, u8p, C.POINTER(C.c_int), u8p]
         getattr(L, f"zkmi_{proto}_aggregate_phase_ms").argtypes = [C.POINTER(C.c_double)]

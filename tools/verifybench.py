@@ -199,19 +199,26 @@ def main_aggregate(protocol):
     import numpy as np
     import fflonk_verify_vectors as FV
     import plonk_verify_vectors as PV
-    from snarkjs_amd import fflonk, fflonk_verify, plonk, plonk_verify, zkmi
+    import verify_vectors as V
+    from snarkjs_amd import fflonk, fflonk_verify, groth16, groth16_verify, plonk, plonk_verify, zkmi
     sizes = [int(x) for x in os.environ.get("VERIFYBENCH_SIZES", "4096,65536,262144").split(",")]
     reps = int(os.environ.get("VERIFYBENCH_REPS", "3"))
     n_distinct = max(64, int(os.environ.get("VERIFYBENCH_DISTINCT", "256")))
     out = {"what": protocol + " aggregated batch verify vs per-proof verify_raw", "reps": reps, "distinct_proofs": n_distinct, "curves": {}}
     gd = os.path.join(ROOT, "tests", "golden")
     L = zkmi.lib()
-    tags = ("plonk_bn128_n2048", "plonk_bls12381_small") if protocol == "plonk" else ("fflonk_bn128_n256",)
-    vec, prover, mod = (PV, plonk, plonk_verify) if protocol == "plonk" else (FV, fflonk, fflonk_verify)
+    tags = {"groth16": ("groth16_bn128_n1024", "groth16_bls12381_n1024"), "plonk": ("plonk_bn128_n2048", "plonk_bls12381_small"), "fflonk": ("fflonk_bn128_n256",)}[protocol]
+    vec, prover, mod = {"groth16": (V, groth16, groth16_verify), "plonk": (PV, plonk, plonk_verify), "fflonk": (FV, fflonk, fflonk_verify)}[protocol]
     for tag in tags:
         vk, pubs, _ = vec.golden(tag + ".json")
-        res_all = prover.prove_many(open(os.path.join(gd, tag + ".zkey"), "rb").read(), [open(os.path.join(gd, tag + ".wtns"), "rb").read()] * n_distinct)
-        distinct = [r["proof"] for r in res_all]
+        zkey, wtns = open(os.path.join(gd, tag + ".zkey"), "rb").read(), open(os.path.join(gd, tag + ".wtns"), "rb").read()
+        if protocol == "groth16":                           # fresh (r, s) per proof: every pi_b differs
+            pk = groth16.ProvingKey(zkey)
+            distinct = [groth16.prove(pk, wtns)["proof"] for _ in range(n_distinct)]
+            pk.release()
+            assert len({tuple(p["pi_b"][0]) for p in distinct}) == n_distinct
+        else:
+            distinct = [r["proof"] for r in prover.prove_many(zkey, [wtns] * n_distinct)]
         key = mod.VerifyingKey(vk)
         r1, p1, ns, _ = key.pack([pubs] * n_distinct, distinct)
         res = {}
@@ -239,11 +246,9 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--protocol", choices=["groth16", "plonk", "fflonk"], default="groth16")
-    ap.add_argument("--aggregate", action="store_true", help="plonk / fflonk: the aggregated check beside the per-proof path")
+    ap.add_argument("--aggregate", action="store_true", help="the aggregated check beside the per-proof path of the same key")
     args = ap.parse_args()
     if args.aggregate:
-        if args.protocol == "groth16":
-            ap.error("--aggregate serves plonk and fflonk")
         main_aggregate(args.protocol)
     else:
         {"groth16": main, "plonk": main_plonk, "fflonk": main_fflonk}[args.protocol]()
