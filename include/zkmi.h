@@ -232,6 +232,33 @@ int zkmi_pipeline_active(void);
 int zkmi_groth16_submit(uint64_t zkey_cache_key, const uint8_t* witness, size_t witness_len, int slot);
 int zkmi_groth16_collect(uint64_t zkey_cache_key, int slot, const uint8_t* r_mont, const uint8_t* s_mont, uint8_t* pi_a, uint8_t* pi_b, uint8_t* pi_c);
 int zkmi_groth16_release(uint64_t zkey_cache_key);
+/* ---- Groth16 setup: zKey.newZKey (src/zkey_new.js) ------------------------------------------------------------------
+ * The device part of newZKey from already-read slices: processConstraints (:203-336), composeAndWritePoints for sections 3, 8, 5, 6, 7
+ * (:338-502, task lists the reference sends straight to its workers: no curve method sees them) and the H points of hashHPoints (:504-577).
+ *   constraints        r1cs section 2 as it lies in the file: per constraint three linear combinations, each u32 n then n x (u32 signal, 32-byte
+ *                      little-endian coefficient). Parsed on the host side of the library in one pass.
+ *   tau_g1 .. beta_tau_g1   the domain_size Lagrange points that start at offset (domain_size - 1) * sG of ptau sections 12, 13, 14, 15.
+ *   tau_g1_powers      the first domain_size + n_h points of ptau section 2; n_h = number of H points the reference hashes: domain_size - 1, or
+ *                      domain_size for domains of 2^15 and above (the chunk loop of :509-513 takes one point more there).
+ * Outputs (caller-owned, lengths checked): ic = section 3 ((n_public + 1) G1), coeffs = section 4 (length from zkmi_groth16_setup_coeffs_len:
+ * records in constraint order, A entries before B entries, then the binding rows, values times R^2 mod r), a, b1 = sections 5, 6 (n_vars G1),
+ * b2 = section 7 (n_vars G2), c = section 8 ((n_vars - n_public - 1) G1): affine Montgomery little-endian, a signal absent from a matrix = all-zero
+ * bytes; h = the n_h differences tauG1[i + domain_size] - tauG1[i], affine, UNCOMPRESSED (big-endian normal form) as they enter the circuit hash.
+ * Fails with ZKMI_ERR_INVALID when a pipeline slot holds work in flight (it uses the active slot's stream). */
+typedef struct zkmi_groth16_setup_in {
+    int curve;
+    uint32_t n_constraints, n_vars, n_public, domain_size, n_h;
+    zkmi_pages constraints, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, tau_g1_powers;
+} zkmi_groth16_setup_in;
+typedef struct zkmi_groth16_setup_out {
+    uint8_t *ic, *coeffs, *a, *b1, *b2, *c, *h;
+    size_t ic_len, coeffs_len, a_len, b1_len, b2_len, c_len, h_len;
+} zkmi_groth16_setup_out;
+/* byte length of section 4 for these constraints; host only, needs no device */
+int zkmi_groth16_setup_coeffs_len(zkmi_pages constraints, uint32_t n_constraints, uint32_t n_public, size_t* len);
+/* section 4 alone (processConstraints, :303-334), out_len as returned above; host only, needs no device */
+int zkmi_groth16_setup_coeffs(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, uint8_t* out, size_t out_len);
+int zkmi_groth16_setup(const zkmi_groth16_setup_in* in, const zkmi_groth16_setup_out* out);
 /* groth16Verify (src/groth16_verify.js:26-87) for batches of proofs against one verifying key, on the device, one verdict per proof.
  * zkmi_groth16_vk_load takes the key's points as the reference's fromObject reads them: (x, y, z) triples in standard form, little-endian,
  * n8q bytes per Fq (Fq2 = c0 | c1); z = 0 infinity, z = 1 affine, other z Jacobian. ic_xyz holds nPublic + 1 points (IC[0..nPublic]).

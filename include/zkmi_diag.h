@@ -103,6 +103,8 @@ int zkmi_groth16_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs_x
                                      int* ok, uint8_t* trace);
 /* lane phase | reduction | tail of the Groth16 verifier's last batch when it was an aggregated one (-1 each otherwise), as above */
 int zkmi_groth16_aggregate_phase_ms(double* lane_reduce_tail);
+/* Device time in ms of the last zkmi_groth16_setup, five values: the evaluate + fold + to-affine launches of A, B1, B2 and IC|C, then the H differences. */
+int zkmi_groth16_setup_phase_ms(double* out5);
 
 #ifdef __cplusplus
 }

@@ -744,6 +744,12 @@ static G16Key* g16_find(uint64_t key) {
     return it == ctx().groth16.end() ? nullptr : (G16Key*)it->second;
 }
 static uint64_t g_last_key = 0;
+// a proof (or its witness half) of some resident key, or an enqueued and uncollected zkmi_msm_table_multi call, sits in a pipeline slot
+bool pipeline_busy() {
+    for (auto& kv : ctx().groth16)
+        for (auto& w : ((G16Key*)kv.second)->wk) if (w.in_flight || w.w_enqueued) return true;
+    return msm_multi_pending(0).live || msm_multi_pending(1).live;
+}
 
 }  // namespace zkmi
 

@@ -83,6 +83,9 @@ struct Ctx {
 Ctx& ctx();
 int require_ctx();
 int select_pipe(int p);
+// true while some pipeline slot holds work that was enqueued and not collected (groth16.hip): an entry point that would use the slot's stream and
+// scratch for something else refuses instead of disturbing it
+bool pipeline_busy();
 // What changes on a box that fetches instructions slowly beyond the instruction cache — bit 0: G1 accumulation of the 14-limb curve runs its
 // Compact instantiation (field29.cuh), 1: the same for its G2 accumulation, 2: Compact G1 row/column sums of that curve, 3: the Fq2 row/column
 // sums go back to the generic 32-bit kernel, 4: PLONK's quotient numerator by the 32-bit kernels with called products (8 - 12 KB per part) instead of the inlined 29-bit ones (41 - 52 KB). ZKMI_COMPACT_CODE=<mask> fixes it; otherwise the box is probed once

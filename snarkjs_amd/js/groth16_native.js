@@ -269,4 +269,4 @@ function makeProver(snarkjs, options) {
     return { prove, proveMany, release };
 }
 
-module.exports = { makeProver, parseZkey, openZkey, descFromSections, toPages, parseWtns, sections };
+module.exports = { makeProver, parseZkey, openZkey, descFromSections, toPages, parseWtns, sections, readerOf, sectionTable };

@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
     if (!curve.__zkmi) return curve;
     const o = curve.__zkmi.orig;
     Object.assign(curve.G1, o.G1);
@@ -202,7 +203,47 @@ async function registerAll(snarkjs, options) {
     const out = {};
     for (const name of ["bn128", "bls12381"]) out[name] = register(await snarkjs.curves.getCurveFromName(name), options);
     if (options && options.fused) out.fused = installFused(snarkjs, options);
+    if (options && options.setup) out.setup = installSetup(snarkjs, options);
     return out;
+}
+
+// ---- zKey.newZKey on the device (opt-in: registerAll(snarkjs, { setup: true })) ---------------------------------------------------------------------
+// newZKey sends its task lists straight to the workers (src/zkey_new.js:338-577), so patching the curve object cannot reach it; like the fused provers it
+// is replaced through the writable PROPERTY snarkjs.zKey. Same signature, inputs (paths, bytes, fastfile descriptors) and result: csHash, or -1 with the
+// reference's logger.error where the reference refuses. One call is handed to the saved reference function: a domain of 2^15 or more that equals the
+// ceremony's power (js/groth16_setup_native.js: the reference's circuit hash reads past the tauG1 section there; INTEGRATION.md 1c).
+function installSetup(snarkjs, options) {
+    if (snarkjs.__zkmiSetup) return snarkjs.__zkmiSetup;
+    const setupN = require("./groth16_setup_native.js");
+    const orig = snarkjs.zKey;
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    async function newZKey(r1csName, ptauName, zkeyName, logger) {
+        let res;
+        try { res = setupN.newZKey(r1csName, ptauName, { addon }); } catch (e) {
+            if (e instanceof setupN.SetupRefusal) {
+                if (e.handOver) return orig.newZKey(r1csName, ptauName, zkeyName, logger);
+                if (e.throws) throw new Error(e.message);
+                if (logger) logger.error(e.message);
+                return -1;
+            }
+            throw e;
+        }
+        if (typeof zkeyName === "string") require("fs").writeFileSync(zkeyName, res.zkey);
+        else if (zkeyName && zkeyName.type === "file") require("fs").writeFileSync(zkeyName.fileName, res.zkey);
+        else if (zkeyName && zkeyName.type === "mem") zkeyName.data = res.zkey;
+        else throw new Error("newZKey: expected a path or a fastfile descriptor for the new key");
+        if (logger) logger.info("Circuit hash: " + Buffer.from(res.csHash).toString("hex"));
+        return res.csHash;
+    }
+    snarkjs.zKey = Object.freeze(Object.assign({}, orig, { newZKey }));
+    snarkjs.__zkmiSetup = { orig };
+    return snarkjs.__zkmiSetup;
+}
+function uninstallSetup(snarkjs) {
+    if (!snarkjs.__zkmiSetup) return;
+    snarkjs.zKey = snarkjs.__zkmiSetup.orig;
+    delete snarkjs.__zkmiSetup;
 }
 
 // ---- the fused provers behind snarkjs.groth16 / plonk / fflonk (opt-in: registerAll(snarkjs, { fused: true })) ------------------------------------
@@ -279,4 +320,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, loadAddon };

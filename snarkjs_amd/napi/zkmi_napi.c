@@ -350,6 +350,43 @@ static napi_value js_group_convert(napi_env env, napi_callback_info info) {
     if (rc) return throw_zkmi(env, rc);
     return NULL;
 }
+/* groth16Setup(curve, nConstraints, nVars, nPublic, domainSize, nH, constraints, tauG1, tauG2, alphaTauG1, betaTauG1, tauG1Powers): zkmi_groth16_setup
+ * (src/zkey_new.js) -> {ic, coeffs, a, b1, b2, c, h}: zkey sections 3, 4, 5, 6, 7, 8 and the uncompressed H differences of the circuit hash */
+static napi_value js_groth16_setup(napi_env env, napi_callback_info info) {
+    ARGS(12);
+    int32_t curve; double num[5];
+    static pages_t pg[6];                  /* main thread only (a synchronous call): too large for the stack six times over */
+    if (get_i32(env, argv[0], &curve) || (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381)) BAD_ARG();
+    for (int i = 0; i < 5; i++) if (get_f64(env, argv[1 + i], &num[i]) || num[i] < 0 || num[i] > 4294967295.0) BAD_ARG();
+    for (int i = 0; i < 6; i++) if (get_pages(env, argv[6 + i], &pg[i])) BAD_ARG();
+    zkmi_groth16_setup_in in;
+    memset(&in, 0, sizeof in);
+    in.curve = curve;
+    in.n_constraints = (uint32_t)num[0]; in.n_vars = (uint32_t)num[1]; in.n_public = (uint32_t)num[2]; in.domain_size = (uint32_t)num[3]; in.n_h = (uint32_t)num[4];
+    in.constraints = as_zk(&pg[0]); in.tau_g1 = as_zk(&pg[1]); in.tau_g2 = as_zk(&pg[2]); in.alpha_tau_g1 = as_zk(&pg[3]); in.beta_tau_g1 = as_zk(&pg[4]);
+    in.tau_g1_powers = as_zk(&pg[5]);
+    if (in.n_vars <= in.n_public) BAD_ARG();
+    zkmi_groth16_setup_out out;
+    memset(&out, 0, sizeof out);
+    int rc = ZK_CALL(zkmi_groth16_setup_coeffs_len(in.constraints, in.n_constraints, in.n_public, &out.coeffs_len));
+    if (rc) return throw_zkmi(env, rc);
+    const size_t sG1 = curve == ZKMI_CURVE_BN128 ? 64 : 96;
+    out.ic_len = ((size_t)in.n_public + 1) * sG1; out.a_len = out.b1_len = (size_t)in.n_vars * sG1; out.b2_len = 2 * out.a_len;
+    out.c_len = ((size_t)in.n_vars - in.n_public - 1) * sG1; out.h_len = (size_t)in.n_h * sG1;
+    static const char* names[7] = {"ic", "coeffs", "a", "b1", "b2", "c", "h"};
+    uint8_t** ptrs[7] = {&out.ic, &out.coeffs, &out.a, &out.b1, &out.b2, &out.c, &out.h};
+    const size_t lens[7] = {out.ic_len, out.coeffs_len, out.a_len, out.b1_len, out.b2_len, out.c_len, out.h_len};
+    napi_value res;
+    NAPI_OK(napi_create_object(env, &res));
+    for (int i = 0; i < 7; i++) {
+        napi_value ta = new_u8(env, lens[i], ptrs[i]);
+        if (!ta) { napi_throw_error(env, NULL, "zkmi: groth16Setup: cannot allocate a section buffer"); return NULL; }
+        NAPI_OK(napi_set_named_property(env, res, names[i], ta));
+    }
+    rc = ZK_CALL(zkmi_groth16_setup(&in, &out));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* joinABC(curve, a, b, c, out, n) */
 static napi_value js_join_abc(napi_env env, napi_callback_info info) {
     ARGS(6);
@@ -1125,7 +1162,7 @@ static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) { 
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
-        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupConvert", js_group_convert},
+        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup},
         {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},

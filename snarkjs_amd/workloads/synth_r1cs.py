@@ -1,0 +1,143 @@
+"""Synthetic .r1cs files (iden3 r1cs binary format, r1csfile) for the Groth16 setup: the fixtures under tests/golden/setup_*, the closed-form
+test and tools/setupbench.py. A constraint is three linear combinations (A, B, C), each a list of (signal, coefficient) in file order; nothing
+here needs the constraints to be satisfiable: newZKey never looks at a witness.
+"""
+import random
+import struct
+
+R = {
+    "bn128": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+    "bls12381": 52435875175126190479447740508185965837690552500527637822603658699938581184513,
+}
+SETUP_SEG = 32          # csrc/groth16_setup.cuh
+
+
+def write_r1cs(curve, n_vars, n_outputs, n_pub_inputs, constraints):
+    """bytes of an .r1cs file; constraints: list of (A, B, C), each a list of (signal, coefficient as a non-negative integer below 2^256)"""
+    body = bytearray()
+    for lcs in constraints:
+        for lc in lcs:
+            body += struct.pack("<I", len(lc))
+            for s, v in lc:
+                body += struct.pack("<I", s) + int(v).to_bytes(32, "little")
+    n_prv = n_vars - 1 - n_outputs - n_pub_inputs
+    head = struct.pack("<I", 32) + R[curve].to_bytes(32, "little") + struct.pack("<IIIIQI", n_vars, n_outputs, n_pub_inputs, n_prv, n_vars, len(constraints))
+    labels = b"".join(struct.pack("<Q", i) for i in range(n_vars))
+    out = bytearray(b"r1cs" + struct.pack("<II", 1, 3))
+    for typ, sec in ((1, head), (2, bytes(body)), (3, labels)):
+        out += struct.pack("<IQ", typ, len(sec)) + sec
+    return bytes(out)
+
+
+def edge_circuit(curve):
+    """cirPower 7, nPublic 2: every corner of the column evaluation (see the comments); (n_vars, n_outputs, n_pub_inputs, constraints)"""
+    r = R[curve]
+    rng = random.Random(0x5e7 + len(curve))
+    wide = [rng.randrange(1 << 200, r) for _ in range(2)]            # two seeded full-width values
+    n_c, n_vars = 110, 12
+    cons = []
+    for c in range(n_c):
+        a, b, cc = [], [], []
+        if c < 3 * SETUP_SEG + 4:                                        # signal 3: one column of 3 SEG + 4 terms in A (cut into four segments), mixed widths
+            a.append((3, [1, r - 1, 2, 1 << 253, 1, wide[0], 1, 5, r - 2][c % 9]))
+        a.append((11, 1 + (c % 3)))
+        b.append((11 if c % 2 else 0, 1 if c % 4 else r - 1))
+        cc.append((10, 1))
+        cons.append([a, b, cc])
+    cons[0][0].append((1, 1)); cons[0][1].append((1, r - 1)); cons[0][2].append((1, 2))        # the public signal 1 in A, B and C
+    cons[1][0].append((2, 7))                                                                  # the public signal 2 in A only
+    cons[2][0].append((4, 3)); cons[2][2].append((4, 1))                                       # signal 4: absent from B
+    #                                                                                            signal 5: absent from every matrix
+    cons[3][0].append((6, 1)); cons[4][1].append((6, r - 1))                                   # signal 6: single-term columns
+    cons[5][0] += [(7, 1), (7, 1)]; cons[5][1] += [(7, 1), (7, 1)]                             # signal 7 twice with 1 and 1: base + base (doubling)
+    cons[6][0] += [(8, 1), (8, r - 1)]; cons[6][1] += [(8, 1), (8, r - 1)]                     # signal 8 twice with 1 and r - 1: sums to infinity
+    cons[7][0] += [(9, 2), (9, 0)]; cons[7][1] += [(9, 1 << 253)]; cons[7][2] += [(9, wide[1])]      # signal 9: 2, 0, 2^253, full width
+    cons[8][1].append((10, wide[0])); cons[9][0].append((10, 0))                               # signal 10: a column that holds only a zero coefficient in A
+    return n_vars, 1, 1, cons
+
+
+def full_circuit(curve, n_c=200, n_vars=60, n_public=3, seed=0xf011):
+    """seeded, sparse, random, one heavy column (signal 5 in every A); cirPower 8 with the defaults"""
+    r = R[curve]
+    rng = random.Random(seed + len(curve))
+
+    def coef():
+        k = rng.random()
+        if k < 0.6:
+            return 1 if rng.random() < 0.5 else r - 1
+        if k < 0.8:
+            return rng.randrange(2, 1 << 16)
+        if k < 0.95:
+            return 1 << rng.randrange(1, 254)
+        return rng.randrange(r)
+
+    def lc(extra=None):
+        sigs = rng.sample(range(n_vars), rng.randrange(1, 5))
+        out = [(s, coef()) for s in sigs if s != extra]
+        if extra is not None:
+            out.append((extra, coef()))
+        return out
+    return n_vars, 1, n_public - 1, [(lc(5), lc(), lc()) for _ in range(n_c)]
+
+
+def one_signal_circuit(curve, n_c, n_vars, n_public, seed):
+    """seeded sparse constraints with signal 0 in every A, B and C (the closed-form test)"""
+    r = R[curve]
+    rng = random.Random(seed)
+
+    def lc():
+        out = [(0, rng.choice([1, r - 1, 2, rng.randrange(r)]))]
+        for s in rng.sample(range(1, n_vars), rng.randrange(0, 3)):
+            out.append((s, rng.choice([1, r - 1, rng.randrange(1, 1 << 20), 1 << rng.randrange(1, 253), rng.randrange(r)])))
+        return out
+    return n_vars, 1, n_public - 1, [(lc(), lc(), lc()) for _ in range(n_c)]
+
+
+def circuit_shaped(curve, lg, seed=1, n_public=2):
+    """-> (r1cs bytes, n_vars): 2^lg - n_public - 1 constraints shaped like a compiled circuit, written with numpy. Rows follow
+    synth_zkey.real_coefs (the distribution behind synth_zkey.make(coef_dist="real"): ~1.5 A terms and ~1 B term per constraint, heavy-tailed rows);
+    on top the COLUMNS get their tail: signal 0 in every 16th A row, signals 1..4 in every 64th; one C term per constraint. Coefficients: 85 % +-1,
+    10 % below 2^16, 5 % powers of two up to 2^253 (Num2Bits)."""
+    import numpy as np
+
+    from . import synth, synth_zkey
+    r = R[curve]
+    n = (1 << lg) - n_public                                            # real_coefs uses rows 0 .. n - 2
+    n_c = n - 1
+    m = max(8, n - 5)
+    mat, con, sig, _in_b = synth_zkey.real_coefs(n, m, n_public, seed)
+    keep = np.arange(mat.size) < mat.size - (n_public + 1)              # without the binding rows: newZKey adds them itself
+    mat, con, sig = mat[keep].astype(np.uint64), con[keep].astype(np.uint64), sig[keep].astype(np.uint64)
+    rows = np.arange(n_c, dtype=np.uint64)
+    extra = [(np.zeros_like(rows[::16]), rows[::16], np.zeros_like(rows[::16]))]
+    extra += [(np.zeros_like(rows[k::64]), rows[k::64], np.full_like(rows[k::64], k)) for k in range(1, 5)]
+    extra.append((np.full_like(rows, 2), rows, np.uint64(5) + (synth.words(seed ^ 0xC0, n_c).astype(np.uint64) % np.uint64(m - 5))))
+    mat = np.concatenate([mat] + [e[0] for e in extra]); con = np.concatenate([con] + [e[1] for e in extra]); sig = np.concatenate([sig] + [e[2] for e in extra])
+    order = np.lexsort((mat, con))
+    mat, con, sig = mat[order], con[order], sig[order]
+    K = mat.size
+    kind = synth.words(seed ^ 0xD0, K).astype(np.uint64)
+    coef = np.zeros((K, 32), np.uint8)
+    sel = kind % np.uint64(100)
+    coef[:, 0] = 1
+    minus = np.frombuffer((r - 1).to_bytes(32, "little"), np.uint8)
+    coef[(sel < 85) & ((kind >> np.uint64(8)) % np.uint64(2) == 1)] = minus
+    small = (sel >= 85) & (sel < 95)
+    coef[small, 0] = ((kind[small] >> np.uint64(8)) % np.uint64(255) + np.uint64(2)).astype(np.uint8)
+    coef[small, 1] = ((kind[small] >> np.uint64(16)) % np.uint64(256)).astype(np.uint8)
+    p2 = np.nonzero(sel >= 95)[0]
+    bit = ((kind[p2] >> np.uint64(8)) % np.uint64(253) + np.uint64(1)).astype(np.int64)
+    coef[p2] = 0
+    coef[p2, bit // 8] = (1 << (bit % 8)).astype(np.uint8)
+    group = (np.uint64(3) * con + mat).astype(np.int64)                 # (constraint, matrix) of every entry
+    counts = np.bincount(group, minlength=3 * n_c).astype(np.uint32)
+    first = np.cumsum(counts) - counts                                  # entries before every group
+    head_pos = 36 * first.astype(np.int64) + 4 * np.arange(3 * n_c, dtype=np.int64)
+    ent_pos = 36 * np.arange(K, dtype=np.int64) + 4 * (group + 1)
+    body = np.zeros(36 * K + 12 * n_c, np.uint8)
+    body[head_pos[:, None] + np.arange(4)] = counts.astype("<u4").view(np.uint8).reshape(-1, 4)
+    rec = np.concatenate([sig.astype("<u4").view(np.uint8).reshape(-1, 4), coef], axis=1)
+    body[ent_pos[:, None] + np.arange(36)] = rec
+    head = struct.pack("<I", 32) + r.to_bytes(32, "little") + struct.pack("<IIIIQI", m, 1, n_public - 1, m - 1 - n_public, m, n_c)
+    out = b"r1cs" + struct.pack("<II", 1, 2) + struct.pack("<IQ", 1, len(head)) + head + struct.pack("<IQ", 2, body.size) + body.tobytes()
+    return out, m

@@ -40,6 +40,7 @@ SYMBOLS = [
     "zkmi_fflonk_vk_load", "zkmi_fflonk_verify_batch", "zkmi_fflonk_vk_release", "zkmi_fflonk_vk_info", "zkmi_fflonk_verify_trace_dev", "zkmi_fflonk_verify_last_ms",
     "zkmi_plonk_verify_aggregate", "zkmi_fflonk_verify_aggregate", "zkmi_plonk_aggregate_trace_dev", "zkmi_fflonk_aggregate_trace_dev", "zkmi_plonk_aggregate_phase_ms",
     "zkmi_fflonk_aggregate_phase_ms", "zkmi_groth16_verify_aggregate", "zkmi_groth16_aggregate_trace_dev", "zkmi_groth16_aggregate_phase_ms",
+    "zkmi_groth16_setup_coeffs_len", "zkmi_groth16_setup_coeffs", "zkmi_groth16_setup", "zkmi_groth16_setup_phase_ms",
 ]
 
 
@@ -80,6 +81,16 @@ class Groth16ZkeyPaged(C.Structure):
     _fields_ = [("curve", C.c_int), ("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain_size", C.c_uint32)] + \
                [(k, Pages) for k in ("coeffs", "bases_a", "bases_b1", "bases_b2", "bases_c", "bases_h")] + \
                [(k, C.c_void_p) for k in ("vk_alpha_1", "vk_beta_1", "vk_beta_2", "vk_delta_1", "vk_delta_2")]
+
+
+class Groth16SetupIn(C.Structure):
+    _fields_ = [("curve", C.c_int)] + [(k, C.c_uint32) for k in ("n_constraints", "n_vars", "n_public", "domain_size", "n_h")] + \
+               [(k, Pages) for k in ("constraints", "tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "tau_g1_powers")]
+
+
+class Groth16SetupOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("ic", "coeffs", "a", "b1", "b2", "c", "h")] + \
+               [(k + "_len", C.c_size_t) for k in ("ic", "coeffs", "a", "b1", "b2", "c", "h")]
 
 
 class _Locked:
@@ -247,6 +258,10 @@ def lib():
         getattr(L, f"zkmi_{proto}_verify_aggregate").argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p, u8p, C.POINTER(C.c_int)]
         getattr(L, f"zkmi_{proto}_aggregate_trace_dev").argtypes = [C.c_uint64, u8p, u8p, C.c_uint32, sz, u8p, u8p, C.POINTER(C.c_int), u8p]
         getattr(L, f"zkmi_{proto}_aggregate_phase_ms").argtypes = [C.POINTER(C.c_double)]
+    L.zkmi_groth16_setup_coeffs_len.argtypes = [Pages, C.c_uint32, C.c_uint32, C.POINTER(sz)]
+    L.zkmi_groth16_setup_coeffs.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, u8p, sz]
+    L.zkmi_groth16_setup.argtypes = [C.POINTER(Groth16SetupIn), C.POINTER(Groth16SetupOut)]
+    L.zkmi_groth16_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
     _lib = _Locked(L)
     return _lib
 
