@@ -8,6 +8,7 @@
 #include "msm29.cuh"
 #include <type_traits>
 #include "zkmi_common.hpp"
+#include "msm_select.hpp"
 
 namespace zkmi {
 
@@ -121,6 +122,17 @@ constexpr int MSM_JOB_SLOTS = 8;
 constexpr size_t MSM_JOB_SLOT_BYTES = 512 * 1024;
 int msm_job_slot(int slot, MsmJob& job);
 
+// Raises a kernel's limit of dynamic LDS to `bytes`, once per kernel and process (every caller of one kernel passes the same size).
+template <auto Kernel> int lds_opt_in(size_t bytes) {
+    static bool opted = false;
+    if (!opted) {
+        ZK_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        opted = true;
+    }
+    return ZKMI_OK;
+}
+static inline int msm_pick_fail(MsmPickError e) { return fail(msm_pick_code(e), msm_pick_message(e)); }
+
 // ---- stage 4: bucket accumulation for one base table over an existing plan ---------------------------------------------
 // skip: the scalar with index i pairs with base (i - skip); indices < skip are ignored. This lets several MSMs share
 // one digit sort (Groth16: A, B1, B2 over the witness and C over witness[nPublic+1:], src/groth16_prove.js:85-97).
@@ -129,139 +141,96 @@ int msm_job_slot(int slot, MsmJob& job);
 // only needed as a sum) and `job` is marked merged: msm_reduce skips it and msm_fold returns the point at infinity for it.
 template <class F> int msm_accumulate(const void* d_bases, const MsmPlan& pl, uint32_t skip, MsmJob& job, const uint32_t* d_infmask = nullptr, MsmJob* into = nullptr) {
     constexpr int FW = FieldWords<F>::value, PW = 4 * FW;
-    constexpr bool WIDE = FW > 12;
+    constexpr bool WIDE = FW > 12;                                     // G2
+    typedef typename F::Cfg C;
+    constexpr int NL = Lim29<C>::NL;
+    static_assert(!WIDE || (Accum29G2<C>::T == msm_wide_block(NL) && MsmAccumBlock<F>::value == msm_wide_block(NL)), "msm_select.hpp: block of the Fq2 kernels");
+    static_assert(G2S_SLOTS == MSM_G2S_LANES, "msm_select.hpp: lanes per block of k_msm_accum29_g2s");
     Ctx& cx = ctx();
     const MsmShape& sh = pl.sh;
     const size_t total = pl.total;
     hipStream_t st = cx.stream;
     const std::string sfx = "." + std::to_string(job.slot);
-    uint32_t *buckets, *lane_partials, *block_partials;
-    const uint32_t* prev_counts = nullptr;
-    if (into) {
-        if (WIDE) return fail(ZKMI_ERR_UNSUPPORTED, "msm_accumulate: merge mode is implemented for G1 only");
-        if (into->W != sh.W || into->c != sh.c || into->nb != sh.nb || !into->buckets) return fail(ZKMI_ERR_INVALID, "msm_accumulate: merge target of a different shape");
-        buckets = const_cast<uint32_t*>(into->buckets);
-        prev_counts = into->counts;
-    } else ZK_TRY(ws_get("msm.buckets" + sfx, total * PW * 4, (void**)&buckets));
-    ZK_TRY(ws_get("msm.lane_partials", std::max<size_t>(pl.multi_bound, 1) * PW * 4, (void**)&lane_partials));
-    const size_t tree_blocks = pl.multi_bound / MSM_TB + 1;
-    ZK_TRY(ws_get("msm.block_partials", tree_blocks * PW * 4, (void**)&block_partials));
-    static bool tree_attr = false;
-    const size_t tree_lds = (size_t)MSM_TB * PW * 4;
-    if (!tree_attr) {
-        ZK_HIP(hipFuncSetAttribute((const void*)k_msm_tree<F, MSM_TB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tree_lds));
-        ZK_HIP(hipFuncSetAttribute((const void*)k_msm_giant<F, MSM_TB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tree_lds));
-        tree_attr = true;
-    }
-    constexpr unsigned AT = WIDE ? MsmAccumBlock<F>::value : 256;      // threads per accumulation block
-    const size_t acc_lds = WIDE ? (size_t)PW * AT * 4 : 0;              // WIDE: XYZZ accumulators live in LDS
-    static bool acc_attr = false;
-    if (WIDE && !acc_attr) {
-        ZK_HIP(hipFuncSetAttribute((const void*)k_msm_accum<F, WIDE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_lds));
-        acc_attr = true;
-    }
-    if (job.acc0) ZK_HIP(hipEventRecord(job.acc0, st));
-    bool launched = false, r29_buckets = false;
-    typedef typename F::Cfg C;
     // base arrays registered in the R'-form of field29.cuh (window tables of resident bases; the library's own upload of a plain zkmi_msm
     // call): the hot loop on unsaturated limbs (9 x 29 bits BN254, 14 x 28 bits BLS12-381)
     auto r29 = cx.r29_tables.find(d_bases);
     const bool table29 = r29 != cx.r29_tables.end();
-    if constexpr (!WIDE) {
-        if (table29) {
-            // ZKMI_R29_REDUCE=0: buckets leave the kernel in the reference's R-form and the generic row / column sums reduce them
-            static const bool r29_reduce = !(getenv("ZKMI_R29_REDUCE") && atoi(getenv("ZKMI_R29_REDUCE")) == 0) && !(getenv("ZKMI_ROWCOL_WAVE") && atoi(getenv("ZKMI_ROWCOL_WAVE")) == 0);
-            launched = true;
-            r29_buckets = into ? into->r29 : (r29_reduce && (sh.c - 1) / 2 >= 6);       // the wave row/column sums need >= 64 buckets per row and column
-            const uint32_t* mask = d_infmask ? d_infmask : r29->second;
-            // Threads per block. A workgroup is placed only when EVERY one of its waves finds registers: a 256-thread block needs a free slot
-            // on all four SIMDs of a CU. While the Fq2 bucket reduction runs beside it on the auxiliary stream (256-register waves on two of the
-            // four SIMDs), a second 14-limb accumulation block (224 registers per wave) no longer fits and the CU drops from eight to four
-            // accumulation waves (r03 trace: B1 4.5 ms against 2.1 ms for the same work alone); 128-thread blocks still fill the other two SIMDs.
-            static const unsigned acc_t_env = getenv("ZKMI_ACC29_BLOCK") ? (unsigned)atoi(getenv("ZKMI_ACC29_BLOCK")) : 0u;
-            const unsigned AT29 = (acc_t_env == 64 || acc_t_env == 128 || acc_t_env == 256) ? acc_t_env : (Lim29<C>::NL > 9 ? 128u : 256u);
-            const dim3 grid((unsigned)((pl.lane_bound + AT29 - 1) / AT29));
-            // compact_code(): the instantiation with CALLED products where the inlined loop exceeds the instruction cache (14-limb curve)
-            // and this box fetches instructions slowly beyond it (field29.cuh: Compact)
-            const bool cc = Lim29<C>::NL > 9 && (compact_code() & 1);
-#define ZK_LAUNCH_ACC29(CC, MG) hipLaunchKernelGGL((k_msm_accum29<CC, MG>), grid, dim3(AT29), 0, st, (const uint32_t*)d_bases, mask, sh, skip, pl.cap, pl.counts, pl.starts, \
-                                                   pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets, lane_partials, prev_counts, (int)r29_buckets)
-            bool done = false;
-            if constexpr (Lim29<C>::NL > 9) if (cc) { if (into) ZK_LAUNCH_ACC29(Compact<C>, true); else ZK_LAUNCH_ACC29(Compact<C>, false); done = true; }
-            if (!done) { if (into) ZK_LAUNCH_ACC29(C, true); else ZK_LAUNCH_ACC29(C, false); }
-#undef ZK_LAUNCH_ACC29
+    const int box = table29 && (WIDE || NL > 9) ? compact_code() : 0;  // the box is probed on first use, and only where a rule of the pick reads it
+    const MsmAccumPick pick = msm_accum_pick(WIDE ? 2 : 1, NL, table29, into != nullptr, into && into->r29, sh.c, box, msm_tuning());
+    if (pick.error == MsmPickError::merge_g2) return msm_pick_fail(pick.error);      // refused before the target is looked at
+    uint32_t *buckets, *lane_partials, *block_partials;
+    const uint32_t* prev_counts = nullptr;
+    if (into) {
+        if (into->W != sh.W || into->c != sh.c || into->nb != sh.nb || !into->buckets) return fail(ZKMI_ERR_INVALID, "msm_accumulate: merge target of a different shape");
+        buckets = const_cast<uint32_t*>(into->buckets);
+        prev_counts = into->counts;
+    } else ZK_TRY(ws_get("msm.buckets" + sfx, total * PW * 4, (void**)&buckets));
+    if (pick.error != MsmPickError::none) return msm_pick_fail(pick.error);          // a target of the right shape in the wrong form
+    ZK_TRY(ws_get("msm.lane_partials", std::max<size_t>(pl.multi_bound, 1) * PW * 4, (void**)&lane_partials));
+    const size_t tree_blocks = pl.multi_bound / MSM_TB + 1;
+    ZK_TRY(ws_get("msm.block_partials", tree_blocks * PW * 4, (void**)&block_partials));
+    const size_t tree_lds = (size_t)MSM_TB * PW * 4;
+    ZK_TRY((lds_opt_in<k_msm_tree<F, MSM_TB>>(tree_lds)));
+    ZK_TRY((lds_opt_in<k_msm_giant<F, MSM_TB>>(tree_lds)));
+    const dim3 grid((unsigned)((pl.lane_bound + pick.lanes_per_block - 1) / pick.lanes_per_block)), block(pick.threads);
+    const uint32_t* mask = d_infmask ? d_infmask : (table29 ? r29->second : nullptr);
+    const int r29_flag = (int)pick.r29_buckets;
+    // one argument list per kernel signature; grid and block come from the pick
+    auto launch29 = [&](auto kernel) {                                 // G1 on unsaturated limbs
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, (const uint32_t*)d_bases, mask, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets,
+                           lane_partials, prev_counts, r29_flag);
+    };
+    auto launch29_g2 = [&](auto kernel, size_t lds) {                  // G2 on unsaturated limbs: no merge mode
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, (const uint32_t*)d_bases, mask, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets,
+                           lane_partials, r29_flag);
+    };
+    auto launch32 = [&](auto kernel, size_t lds) {                     // saturated 32-bit words, R-form buckets
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, (const uint32_t*)d_bases, mask, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets,
+                           lane_partials, prev_counts);
+    };
+    if (job.acc0) ZK_HIP(hipEventRecord(job.acc0, st));
+    typedef MsmAccumKernel K;
+    switch (pick.kernel) {                                             // a case outside its `if constexpr` is one the pick never gives for this F
+    case K::accum29: if constexpr (!WIDE) launch29(k_msm_accum29<C, false>); break;
+    case K::accum29_merge: if constexpr (!WIDE) launch29(k_msm_accum29<C, true>); break;
+    case K::accum29_compact: if constexpr (!WIDE && NL > 9) launch29(k_msm_accum29<Compact<C>, false>); break;
+    case K::accum29_compact_merge: if constexpr (!WIDE && NL > 9) launch29(k_msm_accum29<Compact<C>, true>); break;
+    case K::accum29_g2s: if constexpr (WIDE) launch29_g2(k_msm_accum29_g2s<C>, 0); break;
+    case K::accum29_g2:
+    case K::accum29_g2_compact:
+        if constexpr (WIDE) {
+            constexpr size_t lds29 = Accum29G2<C>::lds_bytes;          // 4 coordinates x 2 components per lane
+            ZK_TRY(lds_opt_in<k_msm_accum29_g2<C>>(lds29));
+            if constexpr (NL > 9) {
+                ZK_TRY(lds_opt_in<k_msm_accum29_g2<Compact<C>>>(lds29));
+                if (pick.kernel == K::accum29_g2_compact) { launch29_g2(k_msm_accum29_g2<Compact<C>>, lds29); break; }
+            }
+            launch29_g2(k_msm_accum29_g2<C>, lds29);
         }
-    } else {
-        if (table29 && into) return fail(ZKMI_ERR_UNSUPPORTED, "msm_accumulate: no merge mode over an R'-form G2 table");
-        if (table29) {
-            launched = true;
-            constexpr unsigned T29 = Accum29G2<C>::T;
-            constexpr size_t lds29 = Accum29G2<C>::lds_bytes;              // 4 coordinates x 2 components per lane
-            static bool a29 = false;
-            if (!a29) {
-                ZK_HIP(hipFuncSetAttribute((const void*)k_msm_accum29_g2<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds29));
-                if constexpr (Lim29<C>::NL > 9) ZK_HIP(hipFuncSetAttribute((const void*)k_msm_accum29_g2<Compact<C>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds29));
-                a29 = true;
-            }
-            // BN254's 72 KB loop loses more to the calls (3.5 -> 7.8 ms on a healthy box) than a slow-fetch box costs it (+8 %): 14-limb curve only
-            const bool cc = Lim29<C>::NL > 9 && (compact_code() & 2) != 0;
-            // The Fq2 buckets stay in R'-form and k_msm_rowcol_wave29_g2 forms the row / column sums on the same limbs (r03 A/B, same box:
-            // BLS12-381 51.1 / 50.2 against 50.3 / 50.0 proofs/s, BN254 105.9 against 105.5); ZKMI_R29_REDUCE_G2=0: R-form buckets and the
-            // generic 32-bit kernel
-            static const bool g2r = !(getenv("ZKMI_R29_REDUCE_G2") && atoi(getenv("ZKMI_R29_REDUCE_G2")) == 0);
-            static const bool wave_ok = !(getenv("ZKMI_ROWCOL_WAVE") && atoi(getenv("ZKMI_ROWCOL_WAVE")) == 0);
-            // on a slow-fetch box (compact_code() bit 3) the Fq2 row / column sums go back to the generic 32-bit kernel, whose 55 - 84 KB of code
-            // was not affected there, instead of the 320 - 750 KB of k_msm_rowcol_wave29_g2 (7.1 instead of 2.1 ms on such a box)
-            r29_buckets = wave_ok && g2r && !(compact_code() & 8) && (sh.c - 1) / 2 >= 6;
-            bool done = false;
-            // r06: one Fq2 component per lane, accumulators in registers (msm29.cuh: k_msm_accum29_g2s) — BN254: 168 VGPRs, 3 waves per SIMD, bit-identical buckets;
-            // BLS12-381: XYZZ in 248 VGPRs without a spill instead of the packed Jacobian in LDS with 111 spilled registers (another representative of the same
-            // bucket), and a hot loop of 61 KB instead of 118 KB — it fits the instruction cache, so it also takes the place of the Compact instantiation on a
-            // slow-fetch box. ZKMI_G2_SPLIT=0: the LDS-parked layouts (and their Compact twin where compact_code() asks for it); ZKMI_G2_SPLIT_BLS=0: 14-limb only
-            {
-                static const bool split_on = !(getenv("ZKMI_G2_SPLIT") && atoi(getenv("ZKMI_G2_SPLIT")) == 0) &&
-                                             !(Lim29<C>::NL > 9 && getenv("ZKMI_G2_SPLIT_BLS") && atoi(getenv("ZKMI_G2_SPLIT_BLS")) == 0);
-                if (split_on) {
-                    hipLaunchKernelGGL((k_msm_accum29_g2s<C>), dim3((unsigned)((pl.lane_bound + G2S_SLOTS - 1) / G2S_SLOTS)), dim3(256), 0, st, (const uint32_t*)d_bases,
-                                       d_infmask ? d_infmask : r29->second, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets,
-                                       lane_partials, (int)r29_buckets);
-                    done = true;
-                }
-            }
-            if constexpr (Lim29<C>::NL > 9) if (cc && !done) {
-                hipLaunchKernelGGL((k_msm_accum29_g2<Compact<C>>), dim3((unsigned)((pl.lane_bound + T29 - 1) / T29)), dim3(T29), lds29, st, (const uint32_t*)d_bases,
-                                   d_infmask ? d_infmask : r29->second, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets,
-                                   lane_partials, (int)r29_buckets);
-                done = true;
-            }
-            if (!done) hipLaunchKernelGGL((k_msm_accum29_g2<C>), dim3((unsigned)((pl.lane_bound + T29 - 1) / T29)), dim3(T29), lds29, st, (const uint32_t*)d_bases,
-                                    d_infmask ? d_infmask : r29->second, sh, skip, pl.cap, pl.counts, pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets, lane_partials,
-                                    (int)r29_buckets);
+        break;
+    case K::accum32: if constexpr (!WIDE) launch32(k_msm_accum<F, false, false>, 0); break;
+    case K::accum32_merge: if constexpr (!WIDE) launch32(k_msm_accum<F, false, true>, 0); break;
+    case K::accum32_wide:
+        if constexpr (WIDE) {
+            const size_t acc_lds = (size_t)PW * pick.threads * 4;      // XYZZ accumulators live in LDS
+            ZK_TRY((lds_opt_in<k_msm_accum<F, true, false>>(acc_lds)));
+            launch32(k_msm_accum<F, true, false>, acc_lds);
         }
+        break;
     }
-    if (into && !launched && into->r29) return fail(ZKMI_ERR_INVALID, "msm_accumulate: merge target holds R'-form buckets");
-    if constexpr (!WIDE) if (into && !launched) {
-        launched = true;
-        hipLaunchKernelGGL((k_msm_accum<F, false, true>), dim3((unsigned)((pl.lane_bound + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_bases, d_infmask, sh, skip, pl.cap, pl.counts,
-                           pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets, lane_partials, prev_counts);
-    }
-    if (!launched)
-        hipLaunchKernelGGL((k_msm_accum<F, WIDE, false>), dim3((unsigned)((pl.lane_bound + AT - 1) / AT)), dim3(AT), acc_lds, st, (const uint32_t*)d_bases, d_infmask, sh, skip, pl.cap, pl.counts,
-                           pl.starts, pl.sorted, pl.lane_g, pl.lane_sub, pl.meta, buckets, lane_partials, prev_counts);
     if (job.acc1) ZK_HIP(hipEventRecord(job.acc1, st));
     if (cx.msm_stats && cx.d_addcount && job.slot < MSM_JOB_SLOTS) {           // outside the bracketed launch
         const int ci = cx.pipe * MSM_JOB_SLOTS + job.slot;
-        const uint32_t* mask = d_infmask ? d_infmask : (table29 ? r29->second : nullptr);
         ZK_HIP(hipMemsetAsync(cx.d_addcount + ci, 0, 8, st));
         hipLaunchKernelGGL(k_msm_count_adds, dim3(1024), dim3(256), 0, st, pl.sorted, pl.counts, pl.starts, (uint32_t)total, skip, mask, cx.d_addcount + ci);
         ZK_HIP(hipMemcpyAsync(cx.h_addcount + ci, cx.d_addcount + ci, 8, hipMemcpyDeviceToHost, st));
     }
     hipLaunchKernelGGL((k_msm_tree<F, MSM_TB>), dim3((unsigned)std::min<size_t>(tree_blocks, 512)), dim3(MSM_TB), tree_lds, st, lane_partials, pl.lane_g, pl.counts, pl.cap, pl.meta, buckets,
-                       block_partials, (int)r29_buckets);
-    hipLaunchKernelGGL((k_msm_giant<F, MSM_TB>), dim3((unsigned)std::min<size_t>(tree_blocks, 256)), dim3(MSM_TB), tree_lds, st, pl.giants, pl.meta, block_partials, buckets, (int)r29_buckets);
+                       block_partials, r29_flag);
+    hipLaunchKernelGGL((k_msm_giant<F, MSM_TB>), dim3((unsigned)std::min<size_t>(tree_blocks, 256)), dim3(MSM_TB), tree_lds, st, pl.giants, pl.meta, block_partials, buckets, r29_flag);
     job.W = sh.W; job.c = sh.c; job.nb = sh.nb; job.buckets = buckets; job.counts = pl.counts;
     job.merged = into != nullptr;
-    job.r29 = r29_buckets;
+    job.r29 = pick.r29_buckets;
     if (into) {
         uint32_t* cmb;
         ZK_TRY(ws_get("msm.cmbcounts." + std::to_string(into->slot), total * 4, (void**)&cmb));
@@ -299,74 +268,55 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
     ZK_TRY(ws_get("msm.redR0" + ax, VW * m2 * PW * 4, (void**)&r0));
     ZK_TRY(ws_get("msm.redA1" + ax, VW * PW * 4, (void**)&a1));
     ZK_TRY(ws_get("msm.redR1" + ax, VW * PW * 4, (void**)&r1));
-    static bool attr_set = false;
-    const size_t lds_ws = (size_t)2 * M * PW * 4;
-    if (!attr_set) {
-        ZK_HIP(hipFuncSetAttribute((const void*)k_msm_wsum<F, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ws));
-        attr_set = true;
-    }
     const size_t n_out = VW * C;
-    // Row/Col sums in stages: L lanes per sum (~16 additions each), then folds of 8 partials at a time
-    // (Fq2 additions are ~50 us of latency each and the total work is small: spread wider and fold 4 at a time)
     constexpr bool WIDE_R = FW > 12;
-    const uint32_t seq = WIDE_R ? 4 : 16, maxL = WIDE_R ? 256 : 64, foldK = WIDE_R ? 4 : 8;
-    uint32_t L = 1;
-    while (L < maxL && (C / L) > seq) L <<= 1;
-    // one wave per sum with the fold inside the launch (k_msm_rowcol_wave) whenever every sum has >= 64 buckets;
-    // ZKMI_ROWCOL_WAVE=0 keeps the staged k_msm_rowcol + k_msm_fold sequence
-    static const bool wave_env = !(getenv("ZKMI_ROWCOL_WAVE") && atoi(getenv("ZKMI_ROWCOL_WAVE")) == 0);
-    const bool wave_rc = wave_env && rbits >= 6 && cbits >= 6;
+    typedef typename F::Cfg Cfg;
+    constexpr int NL = Lim29<Cfg>::NL;
+    static_assert(MsmRcBlock<F>::value == (WIDE_R ? msm_wide_block(NL) : 256u) && (!WIDE_R || Reduce29G2<Cfg>::T == msm_wide_block(NL)), "msm_select.hpp: block of the wave sums");
     bool all_r29 = true;                                     // R'-form buckets and the row / column sums on the same limbs
     for (int i = 0; i < njobs; i++) all_r29 = all_r29 && jobs[i]->r29;
     for (int i = 0; i < njobs; i++) if (jobs[i]->r29 != jobs[0]->r29) return fail(ZKMI_ERR_INVALID, "msm_reduce: jobs with different bucket formats");
-    if (jobs[0]->r29 && !(all_r29 && wave_rc)) return fail(ZKMI_ERR_UNSUPPORTED, "msm_reduce: R'-form buckets need the wave row/column sums");
-    if (all_r29 && wave_rc) {
-        if constexpr (FW <= 12) {
-            typedef typename F::Cfg C;
-            constexpr size_t lds29 = (size_t)256 * 4 * Lim29<C>::NL * 4;
-            static bool rc29_attr = false;
-            if (!rc29_attr) {
-                ZK_HIP(hipFuncSetAttribute((const void*)k_msm_rowcol_wave29<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds29));
-                if constexpr (Lim29<C>::NL > 9) ZK_HIP(hipFuncSetAttribute((const void*)k_msm_rowcol_wave29<Compact<C>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds29));
-                rc29_attr = true;
+    const int box = !WIDE_R && NL > 9 && all_r29 ? compact_code() : 0;      // as in msm_accumulate: only where a rule reads it
+    const MsmRowcolPick rp = msm_rowcol_pick(WIDE_R ? 2 : 1, NL, all_r29, rbits, cbits, aux, box, msm_tuning());
+    if (rp.error != MsmPickError::none) return msm_pick_fail(rp.error);
+    const size_t per_block = rp.threads / 64, rc_blocks = std::min((n_out + per_block - 1) / per_block, rp.max_blocks);
+    auto launch_wave = [&](auto kernel, size_t lds) {         // one wave per sum with the fold inside the launch
+        hipLaunchKernelGGL(kernel, dim3((unsigned)rc_blocks), dim3(rp.threads), lds, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
+    };
+    switch (rp.kernel) {
+    case MsmRowcolKernel::wave29:
+    case MsmRowcolKernel::wave29_compact:
+        if constexpr (!WIDE_R) {
+            constexpr size_t lds29 = (size_t)256 * 4 * NL * 4;
+            ZK_TRY(lds_opt_in<k_msm_rowcol_wave29<Cfg>>(lds29));
+            if constexpr (NL > 9) {
+                ZK_TRY(lds_opt_in<k_msm_rowcol_wave29<Compact<Cfg>>>(lds29));
+                if (rp.kernel == MsmRowcolKernel::wave29_compact) { launch_wave(k_msm_rowcol_wave29<Compact<Cfg>>, lds29); break; }
             }
-            size_t rc_blocks = (n_out + 3) / 4;
-            static const int aux_cap29 = getenv("ZKMI_AUX_RC_SUMS") ? atoi(getenv("ZKMI_AUX_RC_SUMS")) : 512;
-            if (aux && aux_cap29 > 0) rc_blocks = std::min<size_t>(rc_blocks, (size_t)aux_cap29 / 4);
-            // slow-fetch box, 14-limb curve (254 KB inlined): 5.9 -> 3.0 ms there; BN254's 114 KB kernel gains nothing from the calls (measured)
-            bool done = false;
-            if constexpr (Lim29<C>::NL > 9) if (compact_code() & 4) {
-                hipLaunchKernelGGL((k_msm_rowcol_wave29<Compact<C>>), dim3((unsigned)rc_blocks), dim3(256), lds29, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
-                done = true;
-            }
-            if (!done) hipLaunchKernelGGL((k_msm_rowcol_wave29<C>), dim3((unsigned)rc_blocks), dim3(256), lds29, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
-        } else {
-            typedef typename F::Cfg C;
-            constexpr int T = Reduce29G2<C>::T;
-            constexpr size_t lds29 = Reduce29G2<C>::lds_bytes;
-            static bool rc29_attr = false;
-            if (!rc29_attr) { ZK_HIP(hipFuncSetAttribute((const void*)k_msm_rowcol_wave29_g2<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds29)); rc29_attr = true; }
-            size_t rc_blocks = (n_out + T / 64 - 1) / (T / 64);
-            static const int aux_cap29 = getenv("ZKMI_AUX_RC_SUMS") ? atoi(getenv("ZKMI_AUX_RC_SUMS")) : 512;
-            if (aux && aux_cap29 > 0) rc_blocks = std::min<size_t>(rc_blocks, (size_t)aux_cap29 / (T / 64));
-            hipLaunchKernelGGL((k_msm_rowcol_wave29_g2<C>), dim3((unsigned)rc_blocks), dim3(T), lds29, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
+            launch_wave(k_msm_rowcol_wave29<Cfg>, lds29);
         }
-    } else if (wave_rc) {
-        constexpr int T = MsmRcBlock<F>::value;
-        const size_t lds_rc = (size_t)T * PW * 4;
-        static bool rc_attr = false;
-        if (!rc_attr) { ZK_HIP(hipFuncSetAttribute((const void*)k_msm_rowcol_wave<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rc)); rc_attr = true; }
-        size_t rc_blocks = (n_out + T / 64 - 1) / (T / 64);
-        // see k_msm_rowcol_wave: on the auxiliary stream at most aux_cap sums (waves) are in flight, a quarter of the chip's CUs at two
-        // 256-lane blocks per CU; the rest of the CUs stay with the main stream
-        static const int aux_cap = getenv("ZKMI_AUX_RC_SUMS") ? atoi(getenv("ZKMI_AUX_RC_SUMS")) : 512;
-        if (aux && aux_cap > 0) rc_blocks = std::min<size_t>(rc_blocks, (size_t)aux_cap / (T / 64));
-        hipLaunchKernelGGL((k_msm_rowcol_wave<F>), dim3((unsigned)rc_blocks), dim3(T), lds_rc, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
-    } else {
-    uint32_t *p0, *p1;
-    ZK_TRY(ws_get("msm.rcpart0" + ax, n_out * L * PW * 4, (void**)&p0));
-    ZK_TRY(ws_get("msm.rcpart1" + ax, std::max<size_t>(n_out * L / 4, 1) * PW * 4, (void**)&p1));
-    {
+        break;
+    case MsmRowcolKernel::wave29_g2:
+        if constexpr (WIDE_R) {
+            ZK_TRY(lds_opt_in<k_msm_rowcol_wave29_g2<Cfg>>(Reduce29G2<Cfg>::lds_bytes));
+            launch_wave(k_msm_rowcol_wave29_g2<Cfg>, Reduce29G2<Cfg>::lds_bytes);
+        }
+        break;
+    case MsmRowcolKernel::wave: {
+        const size_t lds_rc = (size_t)rp.threads * PW * 4;
+        ZK_TRY(lds_opt_in<k_msm_rowcol_wave<F>>(lds_rc));
+        launch_wave(k_msm_rowcol_wave<F>, lds_rc);
+        break;
+    }
+    case MsmRowcolKernel::staged: {
+        // Row/Col sums in stages: L lanes per sum (~16 additions each), then folds of 8 partials at a time
+        // (Fq2 additions are ~50 us of latency each and the total work is small: spread wider and fold 4 at a time)
+        const uint32_t seq = WIDE_R ? 4 : 16, maxL = WIDE_R ? 256 : 64, foldK = WIDE_R ? 4 : 8;
+        uint32_t L = 1;
+        while (L < maxL && (C / L) > seq) L <<= 1;
+        uint32_t *p0, *p1;
+        ZK_TRY(ws_get("msm.rcpart0" + ax, n_out * L * PW * 4, (void**)&p0));
+        ZK_TRY(ws_get("msm.rcpart1" + ax, std::max<size_t>(n_out * L / 4, 1) * PW * 4, (void**)&p1));
         uint32_t* dst = L == 1 ? rc : p0;
         hipLaunchKernelGGL((k_msm_rowcol<F>), dim3((unsigned)((n_out * L + 255) / 256)), dim3(256), 0, st, rb, (uint32_t)W, nb, rbits, cbits, L, dst);
         uint32_t parts = L;
@@ -378,6 +328,7 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
             hipLaunchKernelGGL((k_msm_fold<F>), dim3((unsigned)((n_out * parts + 255) / 256)), dim3(256), 0, st, src, d2, n_out * parts, K);
             src = d2;
         }
+        break;
     }
     }
     const bool bitsums = VW * (cbits + 1) <= 256;            // few arrays (pre-computed tables): plain sums only, host does the weighting
@@ -385,17 +336,18 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
     const uint32_t* resR = nullptr;
     size_t perA = 0;                                         // words per job in resA
     if (bitsums) {
-        constexpr int MB = (PW * 4 * 256 <= 64 * 1024) ? 256 : 128;
-        static bool battr = false;
-        if (!battr) { ZK_HIP(hipFuncSetAttribute((const void*)k_msm_bitsums<F, MB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MB * PW * 4))); battr = true; }
-        if constexpr (WIDE_R) {
-            constexpr int TB = MsmAccumBlock<F>::value;
-            static bool blattr = false;
-            if (!blattr) { ZK_HIP(hipFuncSetAttribute((const void*)k_msm_bitsums_lds<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(TB * PW * 4))); blattr = true; }
-            if (wave_env) hipLaunchKernelGGL((k_msm_bitsums_lds<F>), dim3((unsigned)(VW * (cbits + 1))), dim3(TB), (size_t)TB * PW * 4, st, rc, C, cbits, a0);
-            else hipLaunchKernelGGL((k_msm_bitsums<F, MB>), dim3((unsigned)(VW * (cbits + 1))), dim3(MB), (size_t)MB * PW * 4, st, rc, C, cbits, a0);
-        } else
-        hipLaunchKernelGGL((k_msm_bitsums<F, MB>), dim3((unsigned)(VW * (cbits + 1))), dim3(MB), (size_t)MB * PW * 4, st, rc, C, cbits, a0);
+        const dim3 bgrid((unsigned)(VW * (cbits + 1)));
+        if (rp.bitsums_lds) {
+            if constexpr (WIDE_R) {                          // G2 only
+                constexpr int TB = MsmAccumBlock<F>::value;
+                ZK_TRY(lds_opt_in<k_msm_bitsums_lds<F>>((size_t)TB * PW * 4));
+                hipLaunchKernelGGL((k_msm_bitsums_lds<F>), bgrid, dim3(TB), (size_t)TB * PW * 4, st, rc, C, cbits, a0);
+            }
+        } else {
+            constexpr int MB = (PW * 4 * 256 <= 64 * 1024) ? 256 : 128;
+            ZK_TRY((lds_opt_in<k_msm_bitsums<F, MB>>((size_t)MB * PW * 4)));
+            hipLaunchKernelGGL((k_msm_bitsums<F, MB>), bgrid, dim3(MB), (size_t)MB * PW * 4, st, rc, C, cbits, a0);
+        }
         resA = a0;
         perA = (size_t)2 * W * (cbits + 1) * PW;
     } else {
@@ -403,6 +355,8 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
         int log_scale = 0;
         const uint32_t *inA = nullptr, *inR = rc;
         uint32_t *outA = a0, *outR = r0;
+        const size_t lds_ws = (size_t)2 * M * PW * 4;
+        ZK_TRY((lds_opt_in<k_msm_wsum<F, M>>(lds_ws)));
         for (;;) {
             const uint32_t blocks = (m + M - 1) / M;
             hipLaunchKernelGGL((k_msm_wsum<F, M>), dim3((unsigned)(VW * blocks)), dim3(M), lds_ws, st, inA, inR, m, blocks, log_scale, outA, outR);
@@ -563,11 +517,10 @@ template <class F> int msm_run_table_multi_enqueue(const void* d_table, size_t s
     int live = 0;
     ZK_HIP(hipEventRecord(cx.ev0, st));
     // The digit sorts are memory-bound, the accumulations ALU-bound: with more than one MSM in the call the sorts go to the
-    // auxiliary stream, so that sort i+1 runs underneath accumulation i (ZKMI_MULTI_OVERLAP=0 keeps one stream).
-    static const bool ov_env = !(getenv("ZKMI_MULTI_OVERLAP") && atoi(getenv("ZKMI_MULTI_OVERLAP")) == 0);
+    // auxiliary stream, so that sort i+1 runs underneath accumulation i (MsmTuning::multi_overlap off keeps one stream).
     int n_live = 0;
     for (int i = 0; i < count; i++) n_live += ks[i] != 0;
-    const bool ov = ov_env && n_live > 1;
+    const bool ov = msm_tuning().multi_overlap && n_live > 1;
     hipStream_t aux = nullptr;
     if (ov) {
         ZK_TRY(ensure_aux_stream());

@@ -106,6 +106,65 @@ def test_non_default_kernel_variants_parity(env):
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+SWITCH_MSM_CASES = [(name, group, lg) for name in CURVES for group in (1, 2) for lg in (11, 14)]
+SWITCH_MSM_SEED = 0x5317C4
+
+
+@pytest.fixture(scope="module")
+def switch_msm_reference():
+    """The results test_msm_kernel_switches_parity expects, computed once for all its settings: the oracle's MSM over the bases 7·11^i·G, and for
+    G2 at 2^14, where the oracle takes too long, the closed form of test_msm_closed_form_large over the same bases."""
+    want = {}
+    for name, group, lg in SWITCH_MSM_CASES:
+        c, n = O.CURVE_ID[name], 1 << lg
+        sc = synth.elems(SWITCH_MSM_SEED + lg, n)
+        if group == 2 and lg == 14:
+            r = int(json.load(open(os.path.join(os.path.dirname(__file__), "golden", f"{name}_kernel_vectors.json")))["r"])
+            k, f = 0, 7
+            for v in sc.reshape(n, 32):
+                k = (k + int.from_bytes(v.tobytes(), "little") * f) % r
+                f = f * 11 % r
+            jac = O.generator_mul(c, group, k)
+        else:
+            jac = O.msm(c, group, O.geom_bases(c, group, n), sc, n, 32)
+        want[name, group, lg] = O.to_affine(c, group, jac)
+    return want
+
+
+@pytest.mark.parametrize("env", [{"ZKMI_ROWCOL_WAVE": "0"}, {"ZKMI_ACC29_BLOCK": "128"}, {"ZKMI_G2_SPLIT_BLS": "0"}],
+                         ids=["staged-rowcol-sums", "accum-128-thread-blocks", "bls-g2-lds-parked-accumulators"])
+def test_msm_kernel_switches_parity(switch_msm_reference, env):
+    """Switch settings of the MSM driver (csrc/msm_select.hpp) that no other test reaches, each in a process of its own (the switches are read once):
+    resident-table MSMs of both curves and both groups at 2^11 terms (c = 11: the staged row / column sums) and 2^14 (c = 15: the wave sums and
+    R'-form buckets), the smallest sizes on either side of that threshold."""
+    import subprocess
+    import sys
+    code = (
+        "import sys, ctypes as C, numpy as np; sys.path[:0] = [%r, %r]\n"
+        "import oracle_lib as O, synth\n"
+        "from snarkjs_amd import zkmi\n"
+        "zkmi.init(0)\n"
+        "L = zkmi.lib()\n"
+        "for name, group, lg in %r:\n"
+        "    c, n = O.CURVE_ID[name], 1 << lg\n"
+        "    d_b = zkmi.DeviceBuffer(n * 2 * group * O.n8q(c))\n"
+        "    zkmi.check(L.zkmi_gen_geometric_bases_dev(c, group, n, 7, 11, d_b.ptr))\n"
+        "    h = C.c_uint64(0)\n"
+        "    zkmi.check(L.zkmi_msm_table_build(c, group, d_b.ptr, n, C.byref(h)))\n"
+        "    d_s = zkmi.DeviceBuffer.from_host(synth.elems(%d + lg, n))\n"
+        "    out = np.zeros(3 * group * O.n8q(c), np.uint8)\n"
+        "    zkmi.check(L.zkmi_msm_table_dev(h, d_s.ptr, n, 32, zkmi.ptr(out)))\n"
+        "    zkmi.check(L.zkmi_msm_table_release(h))\n"
+        "    print('msm', name, group, lg, out.tobytes().hex())\n"
+        "print('switches ok')\n") % (ROOT, os.path.join(ROOT, "tests"), SWITCH_MSM_CASES, SWITCH_MSM_SEED)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    assert r.returncode == 0 and "switches ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    got = {(f[1], int(f[2]), int(f[3])): np.frombuffer(bytes.fromhex(f[4]), np.uint8) for f in (l.split() for l in r.stdout.splitlines()) if f[:1] == ["msm"]}
+    assert sorted(got) == sorted(SWITCH_MSM_CASES)
+    for (name, group, lg), jac in got.items():
+        assert np.array_equal(O.to_affine(O.CURVE_ID[name], group, jac), switch_msm_reference[name, group, lg]), (name, group, lg)
+
+
 @pytest.mark.parametrize("name", CURVES)
 def test_ntt_golden_hashes(zk, golden_dir, name):
     d, cv = load(golden_dir, name), curve_of(zk, name)
