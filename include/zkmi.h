@@ -259,6 +259,45 @@ int zkmi_groth16_setup_coeffs_len(zkmi_pages constraints, uint32_t n_constraints
 /* section 4 alone (processConstraints, :303-334), out_len as returned above; host only, needs no device */
 int zkmi_groth16_setup_coeffs(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, uint8_t* out, size_t out_len);
 int zkmi_groth16_setup(const zkmi_groth16_setup_in* in, const zkmi_groth16_setup_out* out);
+/* ---- PLONK setup: plonk.setup (src/plonk_setup.js) ---------------------------------------------------------------------
+ * Two steps, because the size of everything depends on the gate lowering. (1) zkmi_plonk_setup_lower, host only, needs no device:
+ * processConstraints (:143-302) as one serial pass over r1cs section 2 (`constraints`, as it lies in the file; n_constraints, n_vars, n_public from
+ * the r1cs header). zkmi_plonk_setup_lower_len returns counts4 = plonkNVars, the number of additions, the number of PLONK constraints and domainSize
+ * (2^max(3, log2(constraints - 1) + 1), the reference's log2); the caller puts them into a zkmi_plonk_lowered with buffers of
+ *   additions   n_additions x 72 bytes: zkey section 3 (u32 signal, u32 signal, two Montgomery factors),
+ *   map_a/b/c   n_constraints x u32: sections 4, 5, 6,
+ *   selectors   Qm | Ql | Qr | Qo | Qc, five columns of n_constraints x 32 bytes, Montgomery (what writeQMap :313-318 puts into its buffer),
+ *   pred        3 x domain_size x u32: for position p = column * domain_size + row of the permutation, the position whose value writeSigma
+ *               (:354-422) stores at p: the one that visited p's signal last before p, or the signal's last position for its first one,
+ * and zkmi_plonk_setup_lower fills them (ZKMI_ERR_INVALID when the counts are not those of the constraints). The reference's reading of an r1cs is
+ * kept: one coefficient per signal and linear combination (the last in the file), keys in ascending order, zero coefficients stay.
+ * (2) zkmi_plonk_setup, on the device: lagrange_g1 = the domain_size points that start at offset (domain_size - 1) * sG1 of ptau section 12.
+ * Outputs (caller-owned, lengths checked): q[0..5) = sections 7 - 11 (Qm Ql Qr Qo Qc), each n coefficients then 4n evaluations (writeP4 :326-333,
+ * q_len = 5 n x 32); sigma = section 12 (three such records); lagrange = section 13 (max(n_public, 1) records); commitments = Qm Ql Qr Qo Qc S1
+ * S2 S3 as the header holds them, affine Montgomery, infinity = all-zero bytes. k1 = 2, k2 = 3 (getK1K2 :484-504 cannot return anything else).
+ * Fails with ZKMI_ERR_INVALID when a pipeline slot holds work in flight (it uses the active slot's stream). */
+typedef struct zkmi_plonk_lowered {
+    uint32_t plonk_n_vars, n_additions, n_constraints, domain_size;
+    uint8_t* additions;
+    uint32_t *map_a, *map_b, *map_c;
+    uint8_t* selectors;
+    uint32_t* pred;
+} zkmi_plonk_lowered;
+int zkmi_plonk_setup_lower_len(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, uint32_t* counts4);
+int zkmi_plonk_setup_lower(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, const zkmi_plonk_lowered* out);
+typedef struct zkmi_plonk_setup_in {
+    int curve;
+    uint32_t n_public, n_constraints, domain_size;      /* n_constraints: PLONK constraints (rows of the selector columns) */
+    const uint8_t* selectors;
+    const uint32_t* pred;
+    zkmi_pages lagrange_g1;
+} zkmi_plonk_setup_in;
+typedef struct zkmi_plonk_setup_out {
+    uint8_t* q[5];
+    uint8_t *sigma, *lagrange, *commitments;
+    size_t q_len, sigma_len, lagrange_len, commitments_len;
+} zkmi_plonk_setup_out;
+int zkmi_plonk_setup(const zkmi_plonk_setup_in* in, const zkmi_plonk_setup_out* out);
 /* groth16Verify (src/groth16_verify.js:26-87) for batches of proofs against one verifying key, on the device, one verdict per proof.
  * zkmi_groth16_vk_load takes the key's points as the reference's fromObject reads them: (x, y, z) triples in standard form, little-endian,
  * n8q bytes per Fq (Fq2 = c0 | c1); z = 0 infinity, z = 1 affine, other z Jacobian. ic_xyz holds nPublic + 1 points (IC[0..nPublic]).

@@ -105,6 +105,9 @@ int zkmi_groth16_aggregate_trace_dev(uint64_t vk_handle, const uint8_t* proofs_x
 int zkmi_groth16_aggregate_phase_ms(double* lane_reduce_tail);
 /* Device time in ms of the last zkmi_groth16_setup, five values: the evaluate + fold + to-affine launches of A, B1, B2 and IC|C, then the H differences. */
 int zkmi_groth16_setup_phase_ms(double* out5);
+/* Wall time in ms of the last PLONK setup, four values: the gate lowering on the host (the last zkmi_plonk_setup_lower or _lower_len), then of the last
+ * zkmi_plonk_setup the selector padding and sigma, writeP4 for the eight columns and the Lagrange section, the table build and the eight commitments. */
+int zkmi_plonk_setup_phase_ms(double* out4);
 
 #ifdef __cplusplus
 }

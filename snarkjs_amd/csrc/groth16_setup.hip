@@ -9,49 +9,12 @@
 #include "gconv.cuh"
 #include "groth16_setup.cuh"
 #include "host_field.hpp"
+#include "setup_common.hpp"
 #include "zkmi_common.hpp"
 
 namespace zkmi {
 
 namespace {
-
-struct DevMem {                                   // device memory of one call: freed on every return path
-    std::vector<void*> blocks;
-    ~DevMem() { for (void* p : blocks) (void)hipFree(p); }
-    int get(size_t bytes, void** out) {
-        *out = nullptr;
-        hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-        if (e != hipSuccess) return fail(ZKMI_ERR_HIP, std::string("groth16_setup: hipMalloc: ") + hipGetErrorString(e));
-        blocks.push_back(*out);
-        return ZKMI_OK;
-    }
-};
-
-// sequential reader over a paged buffer
-struct PageReader {
-    const zkmi_pages& pg;
-    int page = 0;
-    size_t off = 0;
-    explicit PageReader(const zkmi_pages& p) : pg(p) {}
-    bool read(void* dst, size_t n) {
-        uint8_t* d = (uint8_t*)dst;
-        while (n) {
-            while (page < pg.n_pages && off == pg.len[page]) { page++; off = 0; }
-            if (page >= pg.n_pages) return false;
-            const size_t k = std::min(n, pg.len[page] - off);
-            if (d) { memcpy(d, pg.ptr[page] + off, k); d += k; }
-            off += k; n -= k;
-        }
-        return true;
-    }
-    bool u32(uint32_t& v) { return read(&v, 4); }
-    bool skip(size_t n) { return read(nullptr, n); }
-};
-size_t pages_bytes(const zkmi_pages& p) {
-    size_t t = 0;
-    for (int i = 0; i < p.n_pages; i++) t += p.len[i];
-    return t;
-}
 
 struct Mag { uint64_t v[4]; bool operator==(const Mag& o) const { return memcmp(v, o.v, sizeof v) == 0; } };
 struct MagHash { size_t operator()(const Mag& m) const { uint64_t h = 0x9e3779b97f4a7c15ull; for (uint64_t x : m.v) h = (h ^ x) * 0xff51afd7ed558ccdull + (h >> 29); return (size_t)h; } };
@@ -206,7 +169,7 @@ template <class F> int run_columns(const ColumnSet& cs, uint32_t n_cols, const u
     constexpr int FW = FieldWords<F>::value;
     Ctx& cx = ctx();
     hipStream_t st = cx.stream;
-    DevMem dm;
+    DevMem dm("groth16_setup");
     const uint32_t n_seg = (uint32_t)cs.segs.size();
     void *d_terms, *d_segs, *d_off, *d_part;
     ZK_TRY(dm.get(cs.terms.size() * sizeof(uint2), &d_terms));
@@ -292,7 +255,7 @@ template <class FqC, class FrC> int setup_run(const zkmi_groth16_setup_in& in, c
     Parsed P;
     ZK_TRY(parse_constraints<FrC>(in, P, out.coeffs, out.coeffs_len));
 
-    DevMem dm;
+    DevMem dm("groth16_setup");
     uint32_t *d_g1, *d_g2, *d_mags, *d_pts;
     ZK_TRY(dm.get(3 * dom * sG1, (void**)&d_g1));                       // tauG1 | alphaTauG1 | betaTauG1
     ZK_TRY(dm.get(dom * sG2, (void**)&d_g2));

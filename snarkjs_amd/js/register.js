@@ -188,6 +188,7 @@ function register(curve, options) {
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
+    if (curve && curve.__zkmiPlonkSetup) uninstallPlonkSetup(curve);    // and the one installed by registerAll(snarkjs, { plonkSetup: true })
     if (!curve.__zkmi) return curve;
     const o = curve.__zkmi.orig;
     Object.assign(curve.G1, o.G1);
@@ -204,6 +205,7 @@ async function registerAll(snarkjs, options) {
     for (const name of ["bn128", "bls12381"]) out[name] = register(await snarkjs.curves.getCurveFromName(name), options);
     if (options && options.fused) out.fused = installFused(snarkjs, options);
     if (options && options.setup) out.setup = installSetup(snarkjs, options);
+    if (options && options.plonkSetup) out.plonkSetup = installPlonkSetup(snarkjs, options);
     return out;
 }
 
@@ -244,6 +246,39 @@ function uninstallSetup(snarkjs) {
     if (!snarkjs.__zkmiSetup) return;
     snarkjs.zKey = snarkjs.__zkmiSetup.orig;
     delete snarkjs.__zkmiSetup;
+}
+
+// ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
+// plonk.setup reaches the device through the patched curve methods alone for its transforms and multiexps; the gate lowering, the permutation, the Lagrange
+// section and the selector buffers stay single-threaded JavaScript (src/plonk_setup.js). Replaced through the writable PROPERTY snarkjs.plonk: same
+// signature, inputs and result (undefined, or -1 with the reference's logger.error where the reference refuses).
+function installPlonkSetup(snarkjs, options) {
+    if (snarkjs.__zkmiPlonkSetup) return snarkjs.__zkmiPlonkSetup;
+    const setupN = require("./plonk_setup_native.js");
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const saved = snarkjs.plonk.setup;
+    async function setup(r1csName, ptauName, zkeyName, logger) {
+        let zkey;
+        try { zkey = setupN.setup(r1csName, ptauName, { addon, logger }); } catch (e) {
+            if (e instanceof setupN.SetupRefusal) { if (logger) logger.error(e.message); return -1; }
+            throw e;
+        }
+        if (typeof zkeyName === "string") require("fs").writeFileSync(zkeyName, zkey);
+        else if (zkeyName && zkeyName.type === "file") require("fs").writeFileSync(zkeyName.fileName, zkey);
+        else if (zkeyName && zkeyName.type === "mem") zkeyName.data = zkey;
+        else throw new Error("plonk.setup: expected a path or a fastfile descriptor for the new key");
+        if (logger) logger.info("Setup Finished");
+    }
+    // the namespace object in place now may already be the fused provers' copy (installFused): keep whatever it holds, replace setup alone
+    snarkjs.plonk = Object.freeze(Object.assign({}, snarkjs.plonk, { setup }));
+    snarkjs.__zkmiPlonkSetup = { saved };
+    return snarkjs.__zkmiPlonkSetup;
+}
+function uninstallPlonkSetup(snarkjs) {
+    if (!snarkjs.__zkmiPlonkSetup) return;
+    snarkjs.plonk = Object.freeze(Object.assign({}, snarkjs.plonk, { setup: snarkjs.__zkmiPlonkSetup.saved }));
+    delete snarkjs.__zkmiPlonkSetup;
 }
 
 // ---- the fused provers behind snarkjs.groth16 / plonk / fflonk (opt-in: registerAll(snarkjs, { fused: true })) ------------------------------------
@@ -320,4 +355,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, loadAddon };

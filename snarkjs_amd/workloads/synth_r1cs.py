@@ -141,3 +141,55 @@ def circuit_shaped(curve, lg, seed=1, n_public=2):
     head = struct.pack("<I", 32) + r.to_bytes(32, "little") + struct.pack("<IIIIQI", m, 1, n_public - 1, m - 1 - n_public, m, n_c)
     out = b"r1cs" + struct.pack("<II", 1, 2) + struct.pack("<IQ", 1, len(head)) + head + struct.pack("<IQ", 2, body.size) + body.tobytes()
     return out, m
+
+
+def plonk_mix_circuit(curve, n_random=24, seed=0x91c):
+    """PLONK setup fixture (src/plonk_setup.js: process): every branch of the gate lowering with nPublic = 0, at most 256 PLONK rows.
+    (n_vars, n_outputs, n_pub_inputs, constraints)"""
+    r = R[curve]
+    rng = random.Random(seed + len(curve))
+    n_vars = 20
+    cons = [
+        ([], [(1, 1)], [(2, 1), (3, 5)]),                                               # A empty
+        ([(1, 1)], [], [(4, r - 1)]),                                                   # B empty
+        ([], [], []),                                                                   # everything empty: a row of zeros
+        ([(0, 3)], [(2, 1), (3, 2)], [(4, 1)]),                                         # A constant-only
+        ([(1, 1), (2, 2)], [(0, 7)], [(5, 1)]),                                         # B constant-only
+        ([(1, 1)], [(0, 0)], [(5, 1)]),                                                 # B constant-only, the constant is zero
+        ([(0, 0)], [(3, 1)], [(6, 1), (0, 9)]),                                         # A constant-only, zero
+        ([(0, r - 1)], [(0, 4)], [(6, 1)]),                                             # A and B constant-only: A wins
+        ([(0, 2), (1, 3)], [(0, 5), (2, 7)], [(0, 11), (3, 13)]),                       # a multiplication with constants in A, B and C
+        ([(1, 1)], [(2, 1)], []),                                                       # a multiplication with C empty
+        ([(1, 1)], [(2, 1)], [(0, 6)]),                                                 # a multiplication with C constant-only
+        ([], [(1, 1)], [(1, 1), (2, 2), (3, 3), (4, 4)]),                               # a sum of 4 terms: one chained addition
+        ([(0, 1)], [(1, 1), (2, r - 2), (3, 3), (4, 1 << 200), (5, 5), (6, 6), (7, 7)], [(8, 1), (0, 1)]),      # 7 + 1 terms through join
+        ([], [], [(7, 1), (6, 2), (5, 3), (4, 4), (3, 5), (2, 6), (1, 7)]),             # a sum of 7 terms, ids descending in the file
+        ([(1, 1), (2, 1)], [(3, 1), (4, 1), (5, 2)], [(6, 1), (7, 1), (8, 1)]),         # multiplications whose sides have 2 and 3 terms
+        ([(9, 1), (3, 2), (0, 4), (5, 1)], [(8, 1), (2, 1)], [(7, 3), (1, 1)]),         # ids out of ascending order, a constant in the middle
+        ([(10, 2), (10, 3)], [(11, 1)], [(12, 1), (12, 0)]),                            # a signal twice: the last coefficient stays
+        ([(13, 0)], [(14, 1)], [(15, 1)]),                                              # a zero coefficient on a signal: still a multiplication
+        ([(2, 1), (1, 1)], [(0, 2)], [(1, 2), (2, 2)]),                                 # join that cancels to zero coefficients (they stay)
+    ]
+    pick = lambda: rng.choice([1, r - 1, 2, rng.randrange(1 << 16), 1 << rng.randrange(1, 253), rng.randrange(r), 0])
+    for _ in range(n_random):
+        lc = lambda lo, hi: [(s, pick()) for s in rng.sample(range(0, n_vars - 1), rng.randrange(lo, hi))]      # signal n_vars - 1 is never used
+        cons.append((lc(0, 4), lc(0, 4), lc(0, 6)))
+    return n_vars, 0, 0, cons
+
+
+def plonk_tiny_circuit(curve):
+    """two constraints and one public signal: three PLONK rows, cirPower clamped to 3"""
+    return 4, 1, 0, [([(2, 1)], [(3, 1)], [(1, 1)]), ([(2, 1)], [(2, 1)], [(3, 1)])]
+
+
+def square_chain(curve, n_c, x0=3, b=5):
+    """x_{i+1} = x_i^2 + b, n_c constraints, satisfiable: signal 1 = x_{n_c} (output), signal 2 = x_0 (public input), signal 2 + i = x_i.
+    -> (n_vars, n_outputs, n_pub_inputs, constraints, witness as a list of integers)"""
+    r = R[curve]
+    x = [x0 % r]
+    for _ in range(n_c):
+        x.append((x[-1] * x[-1] + b) % r)
+    sig = lambda i: 1 if i == n_c else 2 + i
+    cons = [([(sig(i), 1)], [(sig(i), 1)], [(sig(i + 1), 1), (0, (r - b) % r)]) for i in range(n_c)]
+    wit = [1, x[n_c]] + x[:n_c]
+    return n_c + 2, 1, 1, cons, wit

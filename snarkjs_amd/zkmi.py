@@ -41,6 +41,7 @@ SYMBOLS = [
     "zkmi_plonk_verify_aggregate", "zkmi_fflonk_verify_aggregate", "zkmi_plonk_aggregate_trace_dev", "zkmi_fflonk_aggregate_trace_dev", "zkmi_plonk_aggregate_phase_ms",
     "zkmi_fflonk_aggregate_phase_ms", "zkmi_groth16_verify_aggregate", "zkmi_groth16_aggregate_trace_dev", "zkmi_groth16_aggregate_phase_ms",
     "zkmi_groth16_setup_coeffs_len", "zkmi_groth16_setup_coeffs", "zkmi_groth16_setup", "zkmi_groth16_setup_phase_ms",
+    "zkmi_plonk_setup_lower_len", "zkmi_plonk_setup_lower", "zkmi_plonk_setup", "zkmi_plonk_setup_phase_ms",
 ]
 
 
@@ -91,6 +92,21 @@ class Groth16SetupIn(C.Structure):
 class Groth16SetupOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("ic", "coeffs", "a", "b1", "b2", "c", "h")] + \
                [(k + "_len", C.c_size_t) for k in ("ic", "coeffs", "a", "b1", "b2", "c", "h")]
+
+
+class PlonkLowered(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("plonk_n_vars", "n_additions", "n_constraints", "domain_size")] + \
+               [(k, C.c_void_p) for k in ("additions", "map_a", "map_b", "map_c", "selectors", "pred")]
+
+
+class PlonkSetupIn(C.Structure):
+    _fields_ = [("curve", C.c_int)] + [(k, C.c_uint32) for k in ("n_public", "n_constraints", "domain_size")] + \
+               [("selectors", C.c_void_p), ("pred", C.c_void_p), ("lagrange_g1", Pages)]
+
+
+class PlonkSetupOut(C.Structure):
+    _fields_ = [("q", C.c_void_p * 5)] + [(k, C.c_void_p) for k in ("sigma", "lagrange", "commitments")] + \
+               [(k + "_len", C.c_size_t) for k in ("q", "sigma", "lagrange", "commitments")]
 
 
 class _Locked:
@@ -262,6 +278,10 @@ def lib():
     L.zkmi_groth16_setup_coeffs.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, u8p, sz]
     L.zkmi_groth16_setup.argtypes = [C.POINTER(Groth16SetupIn), C.POINTER(Groth16SetupOut)]
     L.zkmi_groth16_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
+    L.zkmi_plonk_setup_lower_len.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.zkmi_plonk_setup_lower.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkLowered)]
+    L.zkmi_plonk_setup.argtypes = [C.POINTER(PlonkSetupIn), C.POINTER(PlonkSetupOut)]
+    L.zkmi_plonk_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
     _lib = _Locked(L)
     return _lib
 

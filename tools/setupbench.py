@@ -1,13 +1,15 @@
-"""Groth16 setup (zkey new): the device newZKey against the reference's WASM newZKey on the same files, on the same box.
+"""Groth16 setup (zkey new) and PLONK setup: the device path against the reference's WASM newZKey / plonk.setup on the same files, on the same box.
 
-    python tools/setupbench.py [--curve bn128] [--cap-s 120] [--max-lg 20] [--out result.json]
+    python tools/setupbench.py [--protocol groth16|plonk] [--curve bn128] [--cap-s 120] [--max-lg 20] [--out result.json]
 
 Per size 2^lg: a circuit-shaped r1cs (snarkjs_amd/workloads/synth_r1cs.py: circuit_shaped) and a prepared ptau synthesised from a known trapdoor
 (only the slices newZKey reads hold points: the Lagrange levels lg and lg + 1 and the tauG1 powers; the other levels are zero bytes). At the first size
 the reference's own newZKey must accept the synthetic ptau and produce the SAME BYTES as the device path, else the tool stops. It starts at 2^12 and
 doubles while the reference leg stays under --cap-s seconds (default 120); beyond that, and at 2^20, the device runs alone. Every ratio printed is
-reference / device on the same key in the same run. Kernel times per section come from zkmi_groth16_setup_phase_ms. Needs a device, node and the
-reference bundle staged in oracle/_ref (make -C oracle _ref)."""
+reference / device on the same key in the same run. Kernel times per section come from zkmi_groth16_setup_phase_ms. With --protocol plonk the same
+files go through snarkjs_amd/plonk_setup.py: setup and the reference's plonk.setup (2^lg is then the size of the r1cs; the PLONK domain is what the gate
+lowering makes of it, reported per row as plonk_constraints and domain_lg together with the four phase times of zkmi_plonk_setup_phase_ms: lowering on the
+host, sigma, P4, commitments; these are host wall times around a stream synchronisation, one sample each, reported as phase_wall_ms, not kernel times). Needs a device, node and the reference bundle staged in oracle/_ref (make -C oracle _ref)."""
 import argparse
 import ctypes as C
 import hashlib
@@ -26,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as O  # noqa: E402
-from snarkjs_amd import groth16_setup as gs, zkmi  # noqa: E402
+from snarkjs_amd import groth16_setup as gs, plonk_setup as ps, zkmi  # noqa: E402
 from snarkjs_amd.workloads import synth_r1cs  # noqa: E402
 
 TRAPDOOR = {"tau": 0x1234567890ABCDEF1234567, "alpha": 0xA1FA0001, "beta": 0xBE7A0002}
@@ -83,8 +85,10 @@ def trapdoor_ptau(curve, lg, path):
         if with_next:
             sec[(2 * d - 1) * sz:(4 * d - 1) * sz] = _points(cid, group, nrm(L2))
         return sec
+    sec3 = np.zeros((1 << power) * s2, np.uint8)
+    sec3[:2 * s2] = _points(cid, 2, nrm(powers[:64]))                   # [1]_2 and [tau]_2: plonk.setup copies the second one into its header (X_2)
     secs = [(1, struct.pack("<I", cv["n8q"]) + q.to_bytes(cv["n8q"], "little") + struct.pack("<II", power, power)),
-            (2, sec2), (3, np.zeros((1 << power) * s2, np.uint8)), (4, _points(cid, 1, nrm(_mont(r, alpha)))), (5, _points(cid, 1, nrm(_mont(r, beta)))),
+            (2, sec2), (3, sec3), (4, _points(cid, 1, nrm(_mont(r, alpha)))), (5, _points(cid, 1, nrm(_mont(r, beta)))),
             (6, _points(cid, 2, nrm(_mont(r, beta)))), (7, struct.pack("<I", 0)),
             (12, lag_section(s1, 1, L, True)), (13, lag_section(s2, 2, L, False)), (14, lag_section(s1, 1, scale(L, alpha), False)), (15, lag_section(s1, 1, scale(L, beta), False))]
     with open(path, "wb") as f:
@@ -97,6 +101,7 @@ def trapdoor_ptau(curve, lg, path):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--protocol", default="groth16", choices=["groth16", "plonk"])
     ap.add_argument("--curve", default="bn128")
     ap.add_argument("--cap-s", type=float, default=120.0, help="the reference leg stops doubling once one run took longer than this")
     ap.add_argument("--min-lg", type=int, default=12)
@@ -117,24 +122,39 @@ def main():
             r1_path, pt_path = os.path.join(tmp, f"c{lg}.r1cs"), os.path.join(tmp, f"p{lg}.ptau")
             data, n_vars = synth_r1cs.circuit_shaped(a.curve, lg)
             open(r1_path, "wb").write(data)
-            trapdoor_ptau(a.curve, lg, pt_path)
-            gs.new_zkey(r1_path, pt_path)                              # warm-up: code objects, allocator
+            plonk = a.protocol == "plonk"
+            pt_lg = lg
+            if plonk:                                                  # the PLONK domain is what the gate lowering makes of the r1cs
+                src = gs._Source(data)
+                sr = gs.read_sections(src, b"r1cs")
+                cv = next(c for c in gs.CURVES.values() if c["name"] == a.curve)
+                pt_lg = ps.lower(cv, gs.read_r1cs_header(src, sr), src.read(*sr[2][0]))["domain_size"].bit_length() - 1
+            trapdoor_ptau(a.curve, pt_lg, pt_path)
+            run = (lambda: (ps.setup(r1_path, pt_path), None)) if plonk else (lambda: gs.new_zkey(r1_path, pt_path))
+            run()                                                      # warm-up: code objects, allocator
             t0 = time.perf_counter()
-            zkey, cs_hash = gs.new_zkey(r1_path, pt_path)
+            zkey, cs_hash = run()
             dev_s = time.perf_counter() - t0
-            ms = (C.c_double * 5)()
-            zkmi.check(zkmi.lib().zkmi_groth16_setup_phase_ms(ms))
-            row = dict(lg=lg, n_vars=n_vars, r1cs_bytes=len(data), device_s=round(dev_s, 4), kernel_ms=dict(zip(("A", "B1", "B2", "IC_C", "H"), [round(x, 3) for x in ms])),
+            ms = (C.c_double * (4 if plonk else 5))()
+            zkmi.check((zkmi.lib().zkmi_plonk_setup_phase_ms if plonk else zkmi.lib().zkmi_groth16_setup_phase_ms)(ms))
+            names = ("lowering_host", "sigma", "p4", "commitments") if plonk else ("A", "B1", "B2", "IC_C", "H")
+            row = dict(lg=lg, n_vars=n_vars, r1cs_bytes=len(data), device_s=round(dev_s, 4),
+                       **{"phase_wall_ms" if plonk else "kernel_ms": dict(zip(names, [round(x, 3) for x in ms]))},
                        zkey_sha256=hashlib.sha256(zkey).hexdigest())
+            if plonk:
+                src = gs._Source(zkey)
+                o = gs.read_sections(src, b"zkey")[2][0][0] + 4 + gs.CURVES[next(k for k, c in gs.CURVES.items() if c["name"] == a.curve)]["n8q"] + 4 + 32
+                _nv, _np, dom, _na, n_pc = struct.unpack_from("<IIIII", zkey, o)
+                row.update(plonk_constraints=n_pc, domain_lg=dom.bit_length() - 1, zkey_bytes=len(zkey))
             if ref_alive:
-                p = subprocess.run([node, "--harmony-optional-chaining", "--harmony-nullish", "--max-old-space-size=16384", os.path.join(ROOT, "tools", "setupbench_ref.js"), r1_path, pt_path],
-                                   capture_output=True, text=True, cwd=ROOT)
+                p = subprocess.run([node, "--harmony-optional-chaining", "--harmony-nullish", "--max-old-space-size=16384", os.path.join(ROOT, "tools", "setupbench_ref.js"), r1_path, pt_path] +
+                                   (["--protocol", "plonk"] if plonk else []), capture_output=True, text=True, cwd=ROOT)
                 if p.returncode != 0:
                     raise SystemExit(f"the reference leg failed at 2^{lg}:\n{p.stderr[-2000:]}")
                 ref = json.loads(p.stdout.strip().splitlines()[-1])
                 row.update(reference_s=round(ref["ms"] / 1e3, 4), reference_threads=ref["threads"], same_bytes=ref["sha256"] == row["zkey_sha256"],
                            ratio=round(ref["ms"] / 1e3 / dev_s, 2))
-                if not row["same_bytes"] or ref["csHash"] != cs_hash.hex():
+                if not row["same_bytes"] or (not plonk and ref["csHash"] != cs_hash.hex()):
                     raise SystemExit(f"2^{lg}: the device key differs from the reference's on the synthetic files: {json.dumps(row)}")
                 if ref["ms"] / 1e3 > a.cap_s:
                     ref_alive = False
@@ -143,7 +163,7 @@ def main():
             os.unlink(r1_path); os.unlink(pt_path)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    res = dict(tool="setupbench", curve=a.curve, cap_s=a.cap_s, rows=rows)
+    res = dict(tool="setupbench", protocol=a.protocol, curve=a.curve, cap_s=a.cap_s, rows=rows)
     if a.out:
         json.dump(res, open(a.out, "w"), indent=1)
 
