@@ -298,6 +298,33 @@ typedef struct zkmi_plonk_setup_out {
     size_t q_len, sigma_len, lagrange_len, commitments_len;
 } zkmi_plonk_setup_out;
 int zkmi_plonk_setup(const zkmi_plonk_setup_in* in, const zkmi_plonk_setup_out* out);
+/* ---- FFLONK setup: fflonk.setup (src/fflonk_setup.js), BN254 -----------------------------------------------------------
+ * The same two steps. (1) zkmi_fflonk_setup_lower, host only, needs no device: computeFFConstraints (:160-209) through
+ * src/r1cs_constraint_processor.js as one serial pass. It fills a zkmi_plonk_lowered (plonk_n_vars = the header's nVars after the lowering), with
+ * these differences: selectors are QL | QR | QM | QO | QC (sections 7 - 11 in that order); zero coefficients leave a combination before it is
+ * classified and after a join; zkmi_fflonk_setup_lower_len's domainSize is 2^max(3, log2(constraints + 1) + 1), which keeps two rows free; in pred
+ * the rows from the constraint count up to domain_size - 3 hold signal 0 and the last two rows point at themselves (the identity, :356-359).
+ * (2) zkmi_fflonk_setup, on the device: tau_g1 = the first 8 * domain_size points of ptau section 2. Outputs (caller-owned, lengths checked):
+ * q[0..5) = sections 7 - 11, sigma = sections 12, 13, 14 one after the other, each record n coefficients then 4n evaluations (q_len = 5 n x 32,
+ * sigma_len = 15 n x 32); lagrange = section 15 (max(n_public, 1) records); c0 = section 17 (8 n x 32: coefficient i of QL QR QO QM QC S1 S2 S3 at
+ * 8 i + j, Montgomery); commitment = [C0]_1 of the header, affine Montgomery. k1 = 2, k2 = 3 (computeK1K2 :513-532 cannot return anything else).
+ * ZKMI_ERR_UNSUPPORTED for BLS12-381 (all three entries: the reference writes BN254's w3 and wr into such a key, so no proof under it verifies) and
+ * for domains above 2^26; ZKMI_ERR_INVALID when a pipeline slot holds work in flight (it uses the active slot's stream). */
+int zkmi_fflonk_setup_lower_len(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, uint32_t* counts4);
+int zkmi_fflonk_setup_lower(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, const zkmi_plonk_lowered* out);
+typedef struct zkmi_fflonk_setup_in {
+    int curve;
+    uint32_t n_public, n_constraints, domain_size;      /* n_constraints: rows of the selector columns */
+    const uint8_t* selectors;
+    const uint32_t* pred;
+    zkmi_pages tau_g1;
+} zkmi_fflonk_setup_in;
+typedef struct zkmi_fflonk_setup_out {
+    uint8_t* q[5];
+    uint8_t *sigma, *lagrange, *c0, *commitment;
+    size_t q_len, sigma_len, lagrange_len, c0_len, commitment_len;
+} zkmi_fflonk_setup_out;
+int zkmi_fflonk_setup(const zkmi_fflonk_setup_in* in, const zkmi_fflonk_setup_out* out);
 /* groth16Verify (src/groth16_verify.js:26-87) for batches of proofs against one verifying key, on the device, one verdict per proof.
  * zkmi_groth16_vk_load takes the key's points as the reference's fromObject reads them: (x, y, z) triples in standard form, little-endian,
  * n8q bytes per Fq (Fq2 = c0 | c1); z = 0 infinity, z = 1 affine, other z Jacobian. ic_xyz holds nPublic + 1 points (IC[0..nPublic]).

@@ -108,6 +108,9 @@ int zkmi_groth16_setup_phase_ms(double* out5);
 /* Wall time in ms of the last PLONK setup, four values: the gate lowering on the host (the last zkmi_plonk_setup_lower or _lower_len), then of the last
  * zkmi_plonk_setup the selector padding and sigma, writeP4 for the eight columns and the Lagrange section, the table build and the eight commitments. */
 int zkmi_plonk_setup_phase_ms(double* out4);
+/* Wall time in ms of the last FFLONK setup, four values: the gate lowering on the host (the last zkmi_fflonk_setup_lower or _lower_len), then of the
+ * last zkmi_fflonk_setup the selector padding and sigma, the transforms of the eight columns and the Lagrange section, the C0 kernel and its commitment. */
+int zkmi_fflonk_setup_phase_ms(double* out4);
 
 #ifdef __cplusplus
 }

@@ -21,9 +21,6 @@ namespace {
 typedef host::HField<4> HF;
 typedef host::HFp<4> E;
 
-struct Term { uint32_t s; E c; };
-typedef std::vector<Term> Lc;                     // a linear combination as the reference holds it: keys ascending, one coefficient per key
-
 struct Lowered {
     uint32_t n_vars = 0;                          // plonkNVars
     std::vector<uint32_t> add_sig;                // 2 per addition
@@ -33,8 +30,6 @@ struct Lowered {
     uint32_t rows() const { return (uint32_t)map[0].size(); }
 };
 
-// src/misc.js log2 on a 32-bit value
-int ref_log2(uint32_t v) { return v ? 31 - __builtin_clz(v) : 0; }
 // cirPower of plonk_setup.js:74-75
 int circuit_power(uint32_t rows) {
     const int p = ref_log2(rows - 1) + 1;
@@ -132,28 +127,7 @@ template <class FrC> int lower(zkmi_pages constraints, uint32_t n_constraints, u
     Lc lc[3];
     std::vector<Term> raw;
     for (uint32_t c = 0; c < n_constraints; c++) {
-        for (int k = 0; k < 3; k++) {
-            uint32_t n;
-            if (!rd.u32(n)) return fail(ZKMI_ERR_INVALID, "plonk_setup: the r1cs constraint section ends inside a constraint");
-            raw.clear();
-            bool sorted = true;
-            for (uint32_t i = 0; i < n; i++) {
-                Term t;
-                if (!rd.u32(t.s) || !rd.read(t.c.v, 32)) return fail(ZKMI_ERR_INVALID, "plonk_setup: the r1cs constraint section ends inside a constraint");
-                if (t.s >= n_vars) return fail(ZKMI_ERR_INVALID, "plonk_setup: a constraint names a signal beyond nVars");
-                // a coefficient of r or more: the reference's reader (r1csfile readConstraints: F.fromRprLE) hands the raw 32 bytes to the WASM
-                // toMontgomery, a Montgomery product with R^2 that ends in one conditional subtraction, so it keeps (c mod r) in Montgomery form for
-                // every c < 2^256. Reducing first (at most 5 subtractions on BN254, 2 on BLS12-381) gives the same element.
-                while (HF::cmp(t.c.v, F.p) >= 0) { uint64_t bw = 0; for (int j = 0; j < 4; j++) { host::u128 d = (host::u128)t.c.v[j] - F.p[j] - bw; t.c.v[j] = (uint64_t)d; bw = (uint64_t)(d >> 64) & 1; } }
-                t.c = F.to_mont(t.c);
-                if (!raw.empty() && raw.back().s >= t.s) sorted = false;
-                raw.push_back(t);
-            }
-            // the reader keeps one coefficient per signal, the last one; `for (s in lc)` then walks the keys in ascending order
-            if (!sorted) std::stable_sort(raw.begin(), raw.end(), [](const Term& x, const Term& y) { return x.s < y.s; });
-            lc[k].clear();
-            for (size_t i = 0; i < raw.size(); i++) if (i + 1 == raw.size() || raw[i + 1].s != raw[i].s) lc[k].push_back(raw[i]);
-        }
+        for (int k = 0; k < 3; k++) ZK_TRY(read_lc(rd, F, n_vars, raw, lc[k], "plonk_setup"));
         ZK_TRY(lw.process(lc[0], lc[1], lc[2]));
     }
     if (L.rows() == 0) return fail(ZKMI_ERR_INVALID, "plonk_setup: a circuit without constraints and without public signals");

@@ -189,6 +189,7 @@ function register(curve, options) {
 function unregister(curve) {
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
     if (curve && curve.__zkmiPlonkSetup) uninstallPlonkSetup(curve);    // and the one installed by registerAll(snarkjs, { plonkSetup: true })
+    if (curve && curve.__zkmiFflonkSetup) uninstallFflonkSetup(curve);  // and by registerAll(snarkjs, { fflonkSetup: true })
     if (!curve.__zkmi) return curve;
     const o = curve.__zkmi.orig;
     Object.assign(curve.G1, o.G1);
@@ -206,6 +207,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.fused) out.fused = installFused(snarkjs, options);
     if (options && options.setup) out.setup = installSetup(snarkjs, options);
     if (options && options.plonkSetup) out.plonkSetup = installPlonkSetup(snarkjs, options);
+    if (options && options.fflonkSetup) out.fflonkSetup = installFflonkSetup(snarkjs, options);
     return out;
 }
 
@@ -279,6 +281,41 @@ function uninstallPlonkSetup(snarkjs) {
     if (!snarkjs.__zkmiPlonkSetup) return;
     snarkjs.plonk = Object.freeze(Object.assign({}, snarkjs.plonk, { setup: snarkjs.__zkmiPlonkSetup.saved }));
     delete snarkjs.__zkmiPlonkSetup;
+}
+
+// ---- fflonk.setup on the device (opt-in: registerAll(snarkjs, { fflonkSetup: true })), BN254 -----------------------------------------------------------
+// Like plonk.setup, fflonk.setup reaches the device through the patched curve methods for its transforms and its one multiexp only; the gate lowering,
+// writeQMap, writeSigma, the Lagrange section and the CPolynomial interleave stay single-threaded JavaScript (src/fflonk_setup.js). Replaced through the
+// writable PROPERTY snarkjs.fflonk: same signature, inputs and result (0; where the reference refuses it throws, and so does this, with the same words).
+// A ceremony on any curve but bn128 goes to the original function: the reference writes BN254's roots into such a key, and opting in changes nothing there.
+function installFflonkSetup(snarkjs, options) {
+    if (snarkjs.__zkmiFflonkSetup) return snarkjs.__zkmiFflonkSetup;
+    const setupN = require("./fflonk_setup_native.js");
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const saved = snarkjs.fflonk.setup;
+    async function setup(r1csName, ptauName, zkeyName, logger) {
+        if (!setupN.isBn128(ptauName)) return saved(r1csName, ptauName, zkeyName, logger);
+        let zkey;
+        try { zkey = setupN.setup(r1csName, ptauName, { addon, logger }); } catch (e) {
+            if (e instanceof setupN.SetupRefusal) throw new Error(e.message);
+            throw e;
+        }
+        if (typeof zkeyName === "string") require("fs").writeFileSync(zkeyName, zkey);
+        else if (zkeyName && zkeyName.type === "file") require("fs").writeFileSync(zkeyName.fileName, zkey);
+        else if (zkeyName && zkeyName.type === "mem") zkeyName.data = zkey;
+        else throw new Error("fflonk.setup: expected a path or a fastfile descriptor for the new key");
+        if (logger) logger.info("FFLONK SETUP FINISHED");
+        return 0;
+    }
+    snarkjs.fflonk = Object.freeze(Object.assign({}, snarkjs.fflonk, { setup }));
+    snarkjs.__zkmiFflonkSetup = { saved };
+    return snarkjs.__zkmiFflonkSetup;
+}
+function uninstallFflonkSetup(snarkjs) {
+    if (!snarkjs.__zkmiFflonkSetup) return;
+    snarkjs.fflonk = Object.freeze(Object.assign({}, snarkjs.fflonk, { setup: snarkjs.__zkmiFflonkSetup.saved }));
+    delete snarkjs.__zkmiFflonkSetup;
 }
 
 // ---- the fused provers behind snarkjs.groth16 / plonk / fflonk (opt-in: registerAll(snarkjs, { fused: true })) ------------------------------------
@@ -355,4 +392,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, loadAddon };

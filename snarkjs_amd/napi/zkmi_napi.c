@@ -390,7 +390,9 @@ static napi_value js_groth16_setup(napi_env env, napi_callback_info info) {
 /* plonkSetupLower(curve, nConstraints, nVars, nPublic, constraints): zkmi_plonk_setup_lower (src/plonk_setup.js processConstraints; host only) ->
  * {plonkNVars, nAdditions, nConstraints, domainSize, additions, mapA, mapB, mapC, selectors, pred}: zkey sections 3 - 6, the five selector columns and
  * the predecessor map that plonkSetup takes */
-static napi_value js_plonk_setup_lower(napi_env env, napi_callback_info info) {
+typedef int (*lower_len_fn)(int, zkmi_pages, uint32_t, uint32_t, uint32_t, uint32_t*);
+typedef int (*lower_fn)(int, zkmi_pages, uint32_t, uint32_t, uint32_t, const zkmi_plonk_lowered*);
+static napi_value setup_lower(napi_env env, napi_callback_info info, lower_len_fn lower_len, lower_fn lower) {
     ARGS(5);
     int32_t curve; double num[3];
     static pages_t pg;                     /* main thread only (a synchronous call) */
@@ -398,7 +400,7 @@ static napi_value js_plonk_setup_lower(napi_env env, napi_callback_info info) {
     for (int i = 0; i < 3; i++) if (get_f64(env, argv[1 + i], &num[i]) || num[i] < 0 || num[i] > 4294967295.0) BAD_ARG();
     if (get_pages(env, argv[4], &pg)) BAD_ARG();
     uint32_t cnt[4];
-    int rc = ZK_CALL(zkmi_plonk_setup_lower_len(curve, as_zk(&pg), (uint32_t)num[0], (uint32_t)num[1], (uint32_t)num[2], cnt));
+    int rc = ZK_CALL(lower_len(curve, as_zk(&pg), (uint32_t)num[0], (uint32_t)num[1], (uint32_t)num[2], cnt));
     if (rc) return throw_zkmi(env, rc);
     zkmi_plonk_lowered low;
     memset(&low, 0, sizeof low);
@@ -412,13 +414,17 @@ static napi_value js_plonk_setup_lower(napi_env env, napi_callback_info info) {
     for (int i = 0; i < 4; i++) { NAPI_OK(napi_create_uint32(env, cnt[i], &v)); NAPI_OK(napi_set_named_property(env, res, cnames[i], v)); }
     for (int i = 0; i < 6; i++) {
         napi_value ta = new_u8(env, lens[i], ptrs[i]);
-        if (!ta) { napi_throw_error(env, NULL, "zkmi: plonkSetupLower: cannot allocate a section buffer"); return NULL; }
+        if (!ta) { napi_throw_error(env, NULL, "zkmi: setup lowering: cannot allocate a section buffer"); return NULL; }
         NAPI_OK(napi_set_named_property(env, res, names[i], ta));
     }
-    rc = ZK_CALL(zkmi_plonk_setup_lower(curve, as_zk(&pg), (uint32_t)num[0], (uint32_t)num[1], (uint32_t)num[2], &low));
+    rc = ZK_CALL(lower(curve, as_zk(&pg), (uint32_t)num[0], (uint32_t)num[1], (uint32_t)num[2], &low));
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
+static napi_value js_plonk_setup_lower(napi_env env, napi_callback_info info) { return setup_lower(env, info, zkmi_plonk_setup_lower_len, zkmi_plonk_setup_lower); }
+/* fflonkSetupLower(curve, nConstraints, nVars, nPublic, constraints): zkmi_fflonk_setup_lower (src/r1cs_constraint_processor.js; host only) -> the same
+ * record as plonkSetupLower: plonkNVars is the header's nVars after the lowering, selectors are QL QR QM QO QC, pred is what fflonkSetup takes */
+static napi_value js_fflonk_setup_lower(napi_env env, napi_callback_info info) { return setup_lower(env, info, zkmi_fflonk_setup_lower_len, zkmi_fflonk_setup_lower); }
 /* plonkSetup(curve, nPublic, nConstraints, domainSize, selectors, pred, lagrangeG1): zkmi_plonk_setup -> {q: [5 sections 7 - 11], sigma, lagrange,
  * commitments}; selectors and pred as plonkSetupLower returned them (nConstraints = its PLONK constraints) */
 static napi_value js_plonk_setup(napi_env env, napi_callback_info info) {
@@ -455,6 +461,46 @@ static napi_value js_plonk_setup(napi_env env, napi_callback_info info) {
         NAPI_OK(napi_set_named_property(env, res, names[i], ta));
     }
     int rc = ZK_CALL(zkmi_plonk_setup(&in, &out));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
+/* fflonkSetup(curve, nPublic, nConstraints, domainSize, selectors, pred, tauG1): zkmi_fflonk_setup -> {q: [5 sections 7 - 11], sigma (sections 12 - 14
+ * one after the other), lagrange, c0, commitment}; selectors and pred as fflonkSetupLower returned them; tauG1 = the first 8 * domainSize points of ptau
+ * section 2 */
+static napi_value js_fflonk_setup(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    int32_t curve; double num[3];
+    static pages_t pg[3];                  /* main thread only (a synchronous call) */
+    if (get_i32(env, argv[0], &curve) || (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381)) BAD_ARG();
+    for (int i = 0; i < 3; i++) if (get_f64(env, argv[1 + i], &num[i]) || num[i] < 0 || num[i] > 4294967295.0) BAD_ARG();
+    for (int i = 0; i < 3; i++) if (get_pages(env, argv[4 + i], &pg[i])) BAD_ARG();
+    zkmi_fflonk_setup_in in;
+    memset(&in, 0, sizeof in);
+    in.curve = curve; in.n_public = (uint32_t)num[0]; in.n_constraints = (uint32_t)num[1]; in.domain_size = (uint32_t)num[2];
+    if (pg[0].n != 1 || pg[1].n != 1 || pg[0].len[0] != (size_t)in.n_constraints * 160 || pg[1].len[0] != (size_t)in.domain_size * 12 || ((uintptr_t)pg[1].ptr[0] & 3)) BAD_ARG();
+    in.selectors = pg[0].ptr[0]; in.pred = (const uint32_t*)pg[1].ptr[0]; in.tau_g1 = as_zk(&pg[2]);
+    const size_t dom = in.domain_size, n_poly = in.n_public ? in.n_public : 1;
+    zkmi_fflonk_setup_out out;
+    memset(&out, 0, sizeof out);
+    out.q_len = 5 * dom * 32; out.sigma_len = 15 * dom * 32; out.lagrange_len = n_poly * 5 * dom * 32; out.c0_len = 8 * dom * 32; out.commitment_len = 64;
+    napi_value res, q;
+    NAPI_OK(napi_create_object(env, &res));
+    NAPI_OK(napi_create_array_with_length(env, 5, &q));
+    for (int i = 0; i < 5; i++) {
+        napi_value ta = new_u8(env, out.q_len, &out.q[i]);
+        if (!ta) { napi_throw_error(env, NULL, "zkmi: fflonkSetup: cannot allocate a section buffer"); return NULL; }
+        NAPI_OK(napi_set_element(env, q, i, ta));
+    }
+    NAPI_OK(napi_set_named_property(env, res, "q", q));
+    static const char* names[4] = {"sigma", "lagrange", "c0", "commitment"};
+    uint8_t** ptrs[4] = {&out.sigma, &out.lagrange, &out.c0, &out.commitment};
+    const size_t lens[4] = {out.sigma_len, out.lagrange_len, out.c0_len, out.commitment_len};
+    for (int i = 0; i < 4; i++) {
+        napi_value ta = new_u8(env, lens[i], ptrs[i]);
+        if (!ta) { napi_throw_error(env, NULL, "zkmi: fflonkSetup: cannot allocate a section buffer"); return NULL; }
+        NAPI_OK(napi_set_named_property(env, res, names[i], ta));
+    }
+    int rc = ZK_CALL(zkmi_fflonk_setup(&in, &out));
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
@@ -1233,7 +1279,7 @@ static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) { 
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
-        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup},
+        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
         {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},

@@ -193,3 +193,33 @@ def square_chain(curve, n_c, x0=3, b=5):
     cons = [([(sig(i), 1)], [(sig(i), 1)], [(sig(i + 1), 1), (0, (r - b) % r)]) for i in range(n_c)]
     wit = [1, x[n_c]] + x[:n_c]
     return n_c + 2, 1, 1, cons, wit
+
+
+def fflonk_quirks_circuit(curve):
+    """FFLONK setup fixture (src/r1cs_constraint_processor.js): every case of the lowering in 14 rows (domain 16), nPublic = 0. Each of the first four
+    constraints gives one row; the multiplication gives ten: its A, B and C each hold five terms, the constant and four signals, so each folds
+    three times. (A combination of five SIGNALS folds four times: three of them would fill the domain alone. plonk_mix_circuit has those.)
+    (n_vars, n_outputs, n_pub_inputs, constraints)"""
+    r = R[curve]
+    cons = [
+        ([(0, 0)], [(1, 1)], []),                                                       # A nullable through an explicit zero coefficient, C empty: a row of zeros
+        ([(1, 1)], [], [(2, r + 3), (3, 1)]),                                           # B nullable (empty); a coefficient >= r
+        ([(0, 2)], [(1, 1), (2, 1)], [(1, 2), (3, 1)]),                                 # A constant: 2 s1 - 2 s1 cancels and leaves the combination
+        ([(4, 5), (5, 1), (4, 2)], [(0, 7)], [(6, 1), (7, 0)]),                         # B constant; signal 4 twice (2 stays); a zero coefficient on signal 7
+        ([(0, 3), (1, 1), (2, 2), (3, 3), (4, 4)], [(8, 2), (0, 5), (5, 1), (6, r - 1), (7, 1 << 200)], [(0, 11), (9, 1), (10, 2), (11, 3), (12, 4)]),
+    ]                                                                                   # signal 13 never occurs
+    return 14, 0, 0, cons
+
+
+def fflonk_rows_circuit(curve, rows, seed=0xff10):
+    """FFLONK setup fixture of exactly `rows` rows with nPublic = 2: every constraint lowers to one row (a product of single terms, or a sum of three).
+    The first rows - 2 constraints do not depend on `rows`, so rows + 1 is the same circuit plus one row. (n_vars, n_outputs, n_pub_inputs, constraints)"""
+    r = R[curve]
+    rng = random.Random(seed + len(curve))
+    n_vars = 12
+    pick = lambda: rng.choice([1, r - 1, 2, rng.randrange(1 << 16), 1 << rng.randrange(1, 253), rng.randrange(1, r)])
+    cons = []
+    for i in range(rows - 2):
+        a, b, c = rng.sample(range(1, n_vars), 3)
+        cons.append(([], [], [(a, pick()), (b, pick()), (c, pick())]) if i % 3 == 2 else ([(a, pick())], [(b, pick())], [(c, pick())]))
+    return n_vars, 1, 1, cons

@@ -42,6 +42,7 @@ SYMBOLS = [
     "zkmi_fflonk_aggregate_phase_ms", "zkmi_groth16_verify_aggregate", "zkmi_groth16_aggregate_trace_dev", "zkmi_groth16_aggregate_phase_ms",
     "zkmi_groth16_setup_coeffs_len", "zkmi_groth16_setup_coeffs", "zkmi_groth16_setup", "zkmi_groth16_setup_phase_ms",
     "zkmi_plonk_setup_lower_len", "zkmi_plonk_setup_lower", "zkmi_plonk_setup", "zkmi_plonk_setup_phase_ms",
+    "zkmi_fflonk_setup_lower_len", "zkmi_fflonk_setup_lower", "zkmi_fflonk_setup", "zkmi_fflonk_setup_phase_ms",
 ]
 
 
@@ -102,6 +103,16 @@ class PlonkLowered(C.Structure):
 class PlonkSetupIn(C.Structure):
     _fields_ = [("curve", C.c_int)] + [(k, C.c_uint32) for k in ("n_public", "n_constraints", "domain_size")] + \
                [("selectors", C.c_void_p), ("pred", C.c_void_p), ("lagrange_g1", Pages)]
+
+
+class FflonkSetupIn(C.Structure):
+    _fields_ = [("curve", C.c_int)] + [(k, C.c_uint32) for k in ("n_public", "n_constraints", "domain_size")] + \
+               [("selectors", C.c_void_p), ("pred", C.c_void_p), ("tau_g1", Pages)]
+
+
+class FflonkSetupOut(C.Structure):
+    _fields_ = [("q", C.c_void_p * 5)] + [(k, C.c_void_p) for k in ("sigma", "lagrange", "c0", "commitment")] + \
+               [(k + "_len", C.c_size_t) for k in ("q", "sigma", "lagrange", "c0", "commitment")]
 
 
 class PlonkSetupOut(C.Structure):
@@ -282,6 +293,10 @@ def lib():
     L.zkmi_plonk_setup_lower.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkLowered)]
     L.zkmi_plonk_setup.argtypes = [C.POINTER(PlonkSetupIn), C.POINTER(PlonkSetupOut)]
     L.zkmi_plonk_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
+    L.zkmi_fflonk_setup_lower_len.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.zkmi_fflonk_setup_lower.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkLowered)]
+    L.zkmi_fflonk_setup.argtypes = [C.POINTER(FflonkSetupIn), C.POINTER(FflonkSetupOut)]
+    L.zkmi_fflonk_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
     _lib = _Locked(L)
     return _lib
 

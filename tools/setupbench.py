@@ -1,6 +1,7 @@
-"""Groth16 setup (zkey new) and PLONK setup: the device path against the reference's WASM newZKey / plonk.setup on the same files, on the same box.
+"""Groth16 setup (zkey new), PLONK setup and FFLONK setup: the device path against the reference's WASM newZKey / plonk.setup / fflonk.setup on the
+same files, on the same box.
 
-    python tools/setupbench.py [--protocol groth16|plonk] [--curve bn128] [--cap-s 120] [--max-lg 20] [--out result.json]
+    python tools/setupbench.py [--protocol groth16|plonk|fflonk] [--curve bn128] [--cap-s 120] [--max-lg 20] [--out result.json]
 
 Per size 2^lg: a circuit-shaped r1cs (snarkjs_amd/workloads/synth_r1cs.py: circuit_shaped) and a prepared ptau synthesised from a known trapdoor
 (only the slices newZKey reads hold points: the Lagrange levels lg and lg + 1 and the tauG1 powers; the other levels are zero bytes). At the first size
@@ -9,7 +10,9 @@ doubles while the reference leg stays under --cap-s seconds (default 120); beyon
 reference / device on the same key in the same run. Kernel times per section come from zkmi_groth16_setup_phase_ms. With --protocol plonk the same
 files go through snarkjs_amd/plonk_setup.py: setup and the reference's plonk.setup (2^lg is then the size of the r1cs; the PLONK domain is what the gate
 lowering makes of it, reported per row as plonk_constraints and domain_lg together with the four phase times of zkmi_plonk_setup_phase_ms: lowering on the
-host, sigma, P4, commitments; these are host wall times around a stream synchronisation, one sample each, reported as phase_wall_ms, not kernel times). Needs a device, node and the reference bundle staged in oracle/_ref (make -C oracle _ref)."""
+host, sigma, P4, commitments; these are host wall times around a stream synchronisation, one sample each, reported as phase_wall_ms, not kernel times). --protocol fflonk does the same through snarkjs_amd/fflonk_setup.py and fflonk.setup (BN254
+only), with a ptau whose first 9 * 2^domain_lg + 18 tauG1 powers are real (fflonk_trapdoor_ptau) and the phases of zkmi_fflonk_setup_phase_ms: lowering on the
+host, sigma, P4, C0 and its commitment. Needs a device, node and the reference bundle staged in oracle/_ref (make -C oracle _ref)."""
 import argparse
 import ctypes as C
 import hashlib
@@ -28,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as O  # noqa: E402
-from snarkjs_amd import groth16_setup as gs, plonk_setup as ps, zkmi  # noqa: E402
+from snarkjs_amd import fflonk_setup as fs, groth16_setup as gs, plonk_setup as ps, zkmi  # noqa: E402
 from snarkjs_amd.workloads import synth_r1cs  # noqa: E402
 
 TRAPDOOR = {"tau": 0x1234567890ABCDEF1234567, "alpha": 0xA1FA0001, "beta": 0xBE7A0002}
@@ -99,9 +102,25 @@ def trapdoor_ptau(curve, lg, path):
             f.write(body)
 
 
+def fflonk_trapdoor_ptau(lg, path):
+    """a BN254 ptau that holds what fflonk.setup reads for a 2^lg domain: the first 9 * 2^lg + 18 tauG1 powers (all real), [1]_2 and [tau]_2, an empty section 12"""
+    cv = next(c for c in gs.CURVES.values() if c["name"] == "bn128")
+    q = next(k for k, c in gs.CURVES.items() if c is cv)
+    cid, r, n = cv["id"], cv["r"], 9 * (1 << lg) + 18
+    tau = TRAPDOOR["tau"] % r
+    powers = O.from_mont(cid, O.apply_key(cid, np.tile(np.asarray(O.fr_one(cid), np.uint8), n), _mont(r, 1), _mont(r, tau)))
+    secs = [(1, struct.pack("<I", 32) + q.to_bytes(32, "little") + struct.pack("<II", lg + 4, lg + 4)), (2, _points(cid, 1, powers).tobytes()),
+            (3, _points(cid, 2, powers[:64]).tobytes()), (12, b"")]
+    with open(path, "wb") as f:
+        f.write(b"ptau" + struct.pack("<II", 1, len(secs)))
+        for typ, body in secs:
+            f.write(struct.pack("<IQ", typ, len(body)))
+            f.write(body)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--protocol", default="groth16", choices=["groth16", "plonk"])
+    ap.add_argument("--protocol", default="groth16", choices=["groth16", "plonk", "fflonk"])
     ap.add_argument("--curve", default="bn128")
     ap.add_argument("--cap-s", type=float, default=120.0, help="the reference leg stops doubling once one run took longer than this")
     ap.add_argument("--min-lg", type=int, default=12)
@@ -122,22 +141,26 @@ def main():
             r1_path, pt_path = os.path.join(tmp, f"c{lg}.r1cs"), os.path.join(tmp, f"p{lg}.ptau")
             data, n_vars = synth_r1cs.circuit_shaped(a.curve, lg)
             open(r1_path, "wb").write(data)
-            plonk = a.protocol == "plonk"
+            plonk, mod = a.protocol != "groth16", fs if a.protocol == "fflonk" else ps          # plonk: either of the two PLONK-style setups
             pt_lg = lg
-            if plonk:                                                  # the PLONK domain is what the gate lowering makes of the r1cs
+            if plonk:                                                  # the domain is what the gate lowering makes of the r1cs
                 src = gs._Source(data)
                 sr = gs.read_sections(src, b"r1cs")
                 cv = next(c for c in gs.CURVES.values() if c["name"] == a.curve)
-                pt_lg = ps.lower(cv, gs.read_r1cs_header(src, sr), src.read(*sr[2][0]))["domain_size"].bit_length() - 1
-            trapdoor_ptau(a.curve, pt_lg, pt_path)
-            run = (lambda: (ps.setup(r1_path, pt_path), None)) if plonk else (lambda: gs.new_zkey(r1_path, pt_path))
+                pt_lg = mod.lower(cv, gs.read_r1cs_header(src, sr), src.read(*sr[2][0]))["domain_size"].bit_length() - 1
+            if a.protocol == "fflonk":
+                fflonk_trapdoor_ptau(pt_lg, pt_path)
+            else:
+                trapdoor_ptau(a.curve, pt_lg, pt_path)
+            run = (lambda: (mod.setup(r1_path, pt_path), None)) if plonk else (lambda: gs.new_zkey(r1_path, pt_path))
             run()                                                      # warm-up: code objects, allocator
             t0 = time.perf_counter()
             zkey, cs_hash = run()
             dev_s = time.perf_counter() - t0
             ms = (C.c_double * (4 if plonk else 5))()
-            zkmi.check((zkmi.lib().zkmi_plonk_setup_phase_ms if plonk else zkmi.lib().zkmi_groth16_setup_phase_ms)(ms))
-            names = ("lowering_host", "sigma", "p4", "commitments") if plonk else ("A", "B1", "B2", "IC_C", "H")
+            L = zkmi.lib()
+            zkmi.check((L.zkmi_fflonk_setup_phase_ms if a.protocol == "fflonk" else L.zkmi_plonk_setup_phase_ms if plonk else L.zkmi_groth16_setup_phase_ms)(ms))
+            names = ("lowering_host", "sigma", "p4", "c0_commitment" if a.protocol == "fflonk" else "commitments") if plonk else ("A", "B1", "B2", "IC_C", "H")
             row = dict(lg=lg, n_vars=n_vars, r1cs_bytes=len(data), device_s=round(dev_s, 4),
                        **{"phase_wall_ms" if plonk else "kernel_ms": dict(zip(names, [round(x, 3) for x in ms]))},
                        zkey_sha256=hashlib.sha256(zkey).hexdigest())
@@ -148,7 +171,7 @@ def main():
                 row.update(plonk_constraints=n_pc, domain_lg=dom.bit_length() - 1, zkey_bytes=len(zkey))
             if ref_alive:
                 p = subprocess.run([node, "--harmony-optional-chaining", "--harmony-nullish", "--max-old-space-size=16384", os.path.join(ROOT, "tools", "setupbench_ref.js"), r1_path, pt_path] +
-                                   (["--protocol", "plonk"] if plonk else []), capture_output=True, text=True, cwd=ROOT)
+                                   (["--protocol", a.protocol] if plonk else []), capture_output=True, text=True, cwd=ROOT)
                 if p.returncode != 0:
                     raise SystemExit(f"the reference leg failed at 2^{lg}:\n{p.stderr[-2000:]}")
                 ref = json.loads(p.stdout.strip().splitlines()[-1])

@@ -1,5 +1,5 @@
-// tools/setupbench_ref.js — the reference leg of tools/setupbench.py: the reference's own WASM zKey.newZKey (or, with --protocol plonk, plonk.setup) on the given files, on this box's host cores.
-//   node --harmony-optional-chaining --harmony-nullish tools/setupbench_ref.js circuit.r1cs prepared.ptau [--protocol plonk]  ->  one JSON line {ms, sha256, csHash}
+// tools/setupbench_ref.js — the reference leg of tools/setupbench.py: the reference's own WASM zKey.newZKey (or, with --protocol plonk | fflonk, plonk.setup | fflonk.setup) on the given files, on this box's host cores.
+//   node --harmony-optional-chaining --harmony-nullish tools/setupbench_ref.js circuit.r1cs prepared.ptau [--protocol plonk|fflonk]  ->  one JSON line {ms, sha256, csHash}
 'use strict';
 const fs = require('fs'), path = require('path'), crypto = require('crypto');
 const snarkjs = require(path.join(__dirname, '..', 'oracle', 'ref_shim.js'));
@@ -8,8 +8,8 @@ const snarkjs = require(path.join(__dirname, '..', 'oracle', 'ref_shim.js'));
     // the bundle is the browser build, which reads a string as a URL: load both files first, outside the timed part
     const r1cs = new Uint8Array(fs.readFileSync(process.argv[2])), ptau = new Uint8Array(fs.readFileSync(process.argv[3]));
     const t0 = process.hrtime.bigint();
-    const plonk = process.argv[4] === '--protocol' && process.argv[5] === 'plonk';
-    const h = plonk ? await snarkjs.plonk.setup(r1cs, ptau, z) : await snarkjs.zKey.newZKey(r1cs, ptau, z);
+    const protocol = process.argv[4] === '--protocol' ? process.argv[5] : 'groth16', plonk = protocol !== 'groth16';
+    const h = protocol === 'fflonk' ? await snarkjs.fflonk.setup(r1cs, ptau, z) : plonk ? await snarkjs.plonk.setup(r1cs, ptau, z) : await snarkjs.zKey.newZKey(r1cs, ptau, z);
     const ms = Number(process.hrtime.bigint() - t0) / 1e6;
     if (h === -1) throw new Error('the reference refused the inputs');
     const data = z.data instanceof Uint8Array ? z.data : z.data.slice(0, z.data.byteLength);
