@@ -117,7 +117,10 @@ int zkmi_msm_table_multi_dev(uint64_t handle, const void* const* d_scalars, cons
  * reductions of the MSMs on the ACTIVE pipeline slot's streams and returns at once; _collect (same slot, same table, same count) waits for them, folds the window sums and writes
  * count x 3*group*n8q bytes. Between the two the host can enqueue the other proof's work — its accumulations then run underneath this call's latency-bound reduction tail.
  * d_scalars must stay valid until the collect; one enqueued call per pipeline slot (an enqueued call that is never collected — its proof was abandoned — is waited for and
- * dropped by the slot's next enqueue). */
+ * dropped by the slot's next enqueue).
+ * Between the two halves the call's window sums sit in pinned host memory of the slot, and the collect folds whatever is there. Every other entry point that uses that
+ * memory in the same slot is therefore REFUSED until the collect (ZKMI_ERR_INVALID, "<entry>: pipeline slot N holds work in flight (collect it first)"): see the rule at
+ * zkmi_pipeline_select below. Transforms, Fr batch operations, the zkmi_poly_* calls, zkmi_to_affine and the batch verifiers take none of it and stay allowed. */
 int zkmi_msm_table_multi_enqueue_dev(uint64_t handle, const void* const* d_scalars, const size_t* ks, int count, size_t scalar_bytes);
 int zkmi_msm_table_multi_collect(uint64_t handle, int count, uint8_t* out_jacobians);
 /* Polynomial.multiExponentiation (src/polynomial/polynomial.js:970-977) for the commitments of one round: the `count` coefficient arrays are MONTGOMERY Fr elements; their
@@ -223,7 +226,19 @@ int zkmi_groth16_submit_dev(uint64_t zkey_cache_key, const void* d_witness, int 
 /* Host-orchestrated provers (plonk.prove, fflonk.prove: the rounds are driven by the host between transcript hashes) with two proofs in flight
  * from ONE host thread: every library call works on the ACTIVE pipeline slot (0 | 1) — its own stream and events, scratch buffers, pool of
  * zkmi_dev_alloc blocks and ring of per-call constants — so the host alternates between two proofs, switching slots at its blocking calls, and
- * the GPU always holds the queued work of the other proof (snarkjs_amd/plonk.py: prove_many). Resident keys and window tables are shared. */
+ * the GPU always holds the queued work of the other proof (snarkjs_amd/plonk.py: prove_many). Resident keys and window tables are shared.
+ *
+ * ONE USER OF A SLOT'S MSM RESULTS AT A TIME. A slot HOLDS WORK IN FLIGHT from zkmi_msm_table_multi_enqueue(_mont)_dev to its zkmi_msm_table_multi_collect, from
+ * zkmi_groth16_submit(_dev) to its zkmi_groth16_collect, and from zkmi_groth16_sums_w_dev to the zkmi_groth16_sums_h_dev that completes it. The per-window sums of that work
+ * land in pinned host memory owned by the slot and are folded by the collect, so while a slot holds work in flight every OTHER entry point that computes an MSM in it fails
+ * with ZKMI_ERR_INVALID and "<entry>: pipeline slot N holds work in flight (collect it first)" before it touches the slot's pinned sums (the Groth16 entry points before
+ * they enqueue anything at all; zkmi_msm and zkmi_msm_dev may already have staged their bases in scratch of their own, stream-ordered behind the work in flight): zkmi_msm, zkmi_msm_dev, zkmi_msm_table_dev,
+ * zkmi_msm_table_multi_dev, a multi-MSM enqueue over a Groth16 proof, and every Groth16 proof (zkmi_groth16_prove*, _submit*, _sums_*) over an enqueued multi-MSM call or over
+ * a proof of ANOTHER resident key (a second submit of the same key keeps its own message). The work in flight is not disturbed by the refused call and collects to its exact
+ * result. Not refused: the collects themselves; an enqueue over this slot's own enqueued multi-MSM call (dropped as abandoned, see above); anything in the OTHER slot;
+ * and everything that computes no MSM (zkmi_ntt*, zkmi_fr_batch*, zkmi_poly_*, zkmi_plonk_* / zkmi_fflonk_* round kernels, zkmi_to_affine, the batch verifiers): the slot's
+ * stream orders their scratch behind the work in flight. zkmi_groth16_prove with a host witness always runs in slot 0, whichever slot is active. The three setups ask for
+ * BOTH slots to be idle. */
 int zkmi_pipeline_select(int slot);
 int zkmi_pipeline_active(void);
 /* The same for a witness in HOST memory (wtns section 2, witness_len = n_vars x 32): it crosses PCIe on the slot's own stream into the

@@ -545,6 +545,7 @@ template <class FrC> static int g16_enqueue(G16Key& K, const void* d_witness, co
     if (phase == G16_H && !Wk.w_enqueued) return fail(ZKMI_ERR_INVALID, "groth16: the witness-side half of this proof has not been enqueued");
     if (phase != G16_H && Wk.w_enqueued) return fail(ZKMI_ERR_INVALID, "groth16: a witness-side half is waiting for its H half in this pipeline slot");
     if (phase == G16_H && !d_h_ext) return fail(ZKMI_ERR_INVALID, "groth16: the H half needs its scalars");
+    ZK_TRY(slot_idle_or_fail("groth16", true, &K));                // another key's proof, or an enqueued multi-MSM call, owns the slot's pinned window sums
     const bool do_w = phase != G16_H, do_h = phase != G16_W, transforms = phase == G16_ALL && !d_h_ext;
     hipStream_t st = cx.stream;
     const uint32_t n = K.domain;
@@ -750,6 +751,21 @@ bool pipeline_busy() {
         for (auto& w : ((G16Key*)kv.second)->wk) if (w.in_flight || w.w_enqueued) return true;
     return msm_multi_pending(0).live || msm_multi_pending(1).live;
 }
+bool pipeline_slot_busy(int pipe, bool multi, const void* own_key) {
+    for (auto& kv : ctx().groth16) {
+        if (kv.second == own_key) continue;
+        const G16Key::Work& w = ((G16Key*)kv.second)->wk[pipe & 1];
+        if (w.in_flight || w.w_enqueued) return true;
+    }
+    return multi && msm_multi_pending(pipe).live;
+}
+// The ONLY place the busy-slot message is composed (msm_host.hpp and the entry points below call this). js/device_queue.js matches its wording
+// (/pipeline slot \d holds work in flight/) to make a Groth16 call once more that lost a race against a synchronous prover, and the tests match it too: reword all together.
+int slot_idle_or_fail(const char* entry, bool multi, const void* own_key) {
+    const int pipe = ctx().pipe;
+    if (!pipeline_slot_busy(pipe, multi, own_key)) return ZKMI_OK;
+    return fail(ZKMI_ERR_INVALID, std::string(entry) + ": pipeline slot " + std::to_string(pipe) + " holds work in flight (collect it first)");
+}
 
 }  // namespace zkmi
 
@@ -888,6 +904,7 @@ int zkmi_groth16_submit(uint64_t key, const uint8_t* witness, size_t witness_len
     g_last_key = key;
     int rc = g16_work_alloc(*K, slot);
     if (!rc && K->wk[slot].in_flight) rc = fail(ZKMI_ERR_INVALID, "groth16: this pipeline slot already holds a proof in flight (collect it first)");
+    if (!rc) rc = slot_idle_or_fail("groth16_submit", true, K);      // before the witness upload: a refused call enqueues nothing
     if (!rc && hipMemcpyAsync(K->wk[slot].w, witness, witness_len, hipMemcpyHostToDevice, ctx().stream) != hipSuccess) rc = fail(ZKMI_ERR_HIP, "groth16_submit: witness upload");
     if (!rc) rc = K->curve == ZKMI_CURVE_BN128 ? g16_enqueue<Bn254Fr>(*K, K->wk[slot].w) : g16_enqueue<Bls12381Fr>(*K, K->wk[slot].w);
     int rc2 = select_pipe(0);
@@ -949,6 +966,10 @@ static int g16_prove_host(const zkmi_groth16_zkey_paged* zkey, uint64_t key, con
         return fail(ZKMI_ERR_INVALID, msg);
     }
     ZK_TRY(select_pipe(0));
+    {   // before the witness upload: a refused call enqueues nothing (a key loaded for this one call is released again)
+        const int busy = slot_idle_or_fail("groth16_prove", true, K);
+        if (busy) { const std::string msg = zkmi_last_error(); if (!key) zkmi_groth16_release(k); return fail(busy, msg); }
+    }
     ZK_HIP(hipMemcpyAsync(K->wk[0].w, witness, (size_t)K->n_vars * 32, hipMemcpyHostToDevice, ctx().stream));
     int rc = zkmi_groth16_prove_dev(k, K->wk[0].w, r_mont, s_mont, pi_a, pi_b, pi_c);
     if (!key) zkmi_groth16_release(k);

@@ -414,6 +414,7 @@ template <class F> int msm_run(const void* d_bases, const void* d_scalars, size_
     hipStream_t st = cx.stream;
     MsmPlan pl;
     MsmJob job;
+    ZK_TRY(slot_idle_or_fail("msm"));
     ZK_TRY(msm_job_slot(0, job));
     if (!cx.ev0_held) ZK_HIP(hipEventRecord(cx.ev0, st));
     ZK_TRY(msm_sort(d_scalars, n, sb, pl));
@@ -476,6 +477,7 @@ template <class F> int msm_run_table(const void* d_table, size_t stride, int c, 
     hipStream_t st = cx.stream;
     MsmPlan pl;
     MsmJob job;
+    ZK_TRY(slot_idle_or_fail("msm_table"));
     ZK_TRY(msm_job_slot(0, job));
     ZK_HIP(hipEventRecord(cx.ev0, st));
     ZK_TRY(msm_sort(d_scalars, k, sb, pl, 0, c, stride));
@@ -507,6 +509,7 @@ template <class F> int msm_run_table_multi_enqueue(const void* d_table, size_t s
     if (count < 1 || count > MSM_MAX_BATCH) return fail(ZKMI_ERR_INVALID, "msm_table_multi: 1..4 MSMs per call");
     MsmMultiPending& P = msm_multi_pending(cx.pipe);
     hipStream_t st = cx.stream;
+    ZK_TRY(slot_idle_or_fail("msm_table_multi", false));              // a Groth16 proof in flight; this slot's own abandoned call is dropped below instead
     if (P.live) {                                                      // a call that was enqueued and never collected (its proof was abandoned after an error): drop it
         ZK_HIP(hipStreamSynchronize(st));
         P.live = false;
@@ -569,6 +572,7 @@ template <class F> int msm_run_table_multi_collect(int count, uint8_t* out_jacs)
     return ZKMI_OK;
 }
 template <class F> int msm_run_table_multi(const void* d_table, size_t stride, int c, const void* const* d_scalars, const size_t* ks, int count, size_t sb, uint8_t* out_jacs) {
+    ZK_TRY(slot_idle_or_fail("msm_table_multi_dev"));                 // the one-call form abandons nothing: over an enqueued call it is refused like any other MSM
     int rc = msm_run_table_multi_enqueue<F>(d_table, stride, c, d_scalars, ks, count, sb);
     if (rc) { msm_multi_pending(ctx().pipe).live = false; return rc; }
     return msm_run_table_multi_collect<F>(count, out_jacs);

@@ -86,6 +86,12 @@ int select_pipe(int p);
 // true while some pipeline slot holds work that was enqueued and not collected (groth16.hip): an entry point that would use the slot's stream and
 // scratch for something else refuses instead of disturbing it
 bool pipeline_busy();
+// The same question for ONE slot, asked by everything that takes the slot's pinned MSM job slots (msm_job_slot: msm_run, msm_run_table, the multi-MSM enqueue, a Groth16
+// enqueue): the window sums of the work in flight land there and are folded on the host at its collect, so another taker in between would hand that collect its own sums.
+// multi: count an enqueued and uncollected zkmi_msm_table_multi call (its own re-enqueue drops it instead); own_key: a G16Key whose state in this slot is the caller's own
+// (the H half after the witness-side half). slot_idle_or_fail fails with ZKMI_ERR_INVALID and "<entry>: pipeline slot N holds work in flight (collect it first)".
+bool pipeline_slot_busy(int pipe, bool multi = true, const void* own_key = nullptr);
+int slot_idle_or_fail(const char* entry, bool multi = true, const void* own_key = nullptr);
 // What changes on a box that fetches instructions slowly beyond the instruction cache — bit 0: G1 accumulation of the 14-limb curve runs its
 // Compact instantiation (field29.cuh), 1: the same for its G2 accumulation, 2: Compact G1 row/column sums of that curve, 3: the Fq2 row/column
 // sums go back to the generic 32-bit kernel, 4: PLONK's quotient numerator by the 32-bit kernels with called products (8 - 12 KB per part) instead of the inlined 29-bit ones (41 - 52 KB). ZKMI_COMPACT_CODE=<mask> fixes it; otherwise the box is probed once

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import zkmi
 from .groth16 import _curve_from_q
-from .plonk import _Field, _Poly, _Transcript, evaluate_many, lincomb
+from .plonk import Enqueued, _Field, _Poly, _Transcript, evaluate_many, lincomb
 
 
 class FflonkKey:
@@ -276,7 +276,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     if _degree(C1) >= 8 * n - 8:
         raise ValueError("C1 Polynomial is not well calculated")
     cm = _commit_enqueue(key, C1)
-    yield
+    yield Enqueued(key.ptau_table, 1)
     pts["C1"] = _commit_collect(cm)
 
     # ---- ROUND 2 (:558-862)
@@ -317,7 +317,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     if _degree(C2) >= 9 * n:
         raise ValueError("C2 Polynomial is not well calculated")
     cm = _commit_enqueue(key, C2)
-    yield
+    yield Enqueued(key.ptau_table, 1)
     pts["C2"] = _commit_collect(cm)
 
     # ---- ROUND 3 (:864-963)
@@ -370,7 +370,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     if _degree(F) >= 9 * n - 6:
         raise ValueError("F Polynomial is not well calculated")
     cm = _commit_enqueue(key, F)
-    yield
+    yield Enqueued(key.ptau_table, 1)
     pts["W1"] = _commit_collect(cm)
 
     # ---- ROUND 5 (:1059-1180)
@@ -398,7 +398,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     if _degree(Lp) >= 9 * n - 1:
         raise ValueError("Degree of L(X)/(ZTS2(y)(X-y)) is not correct")
     cm = _commit_enqueue(key, Lp)
-    yield
+    yield Enqueued(key.ptau_table, 1)
     pts["W2"] = _commit_collect(cm)
 
     # ---- getMontgomeryBatchedInverse (:1182-1287)

@@ -106,8 +106,9 @@ function prove(zkey, wtns, blindingMont = null, options = null) {
         if (!(zkey instanceof FflonkKey)) key.release();
     }
 }
-// async like the reference's fflonkProve (src/fflonk_prove.js:51): the commitment waits on a libuv pool thread; serialised per process
-let asyncQueue = Promise.resolve();
+// async like the reference's fflonkProve (src/fflonk_prove.js:51): the commitment waits on a libuv pool thread; serialised per process, together with the
+// PLONK and Groth16 provers (js/device_queue.js)
+const { exclusive } = require("./device_queue.js");
 function proveAsync(zkey, wtns, blindingMont = null, options = null) {
     const run = async () => {
         const key = zkey instanceof FflonkKey ? zkey : new FflonkKey(zkey, options);
@@ -123,9 +124,7 @@ function proveAsync(zkey, wtns, blindingMont = null, options = null) {
             if (!(zkey instanceof FflonkKey)) key.release();
         }
     };
-    const p = asyncQueue.then(run, run);
-    asyncQueue = p.catch(() => {});
-    return p;
+    return exclusive(run);
 }
 
 function* proveSteps(key, wt, blindingMont, track) {

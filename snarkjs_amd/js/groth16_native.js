@@ -146,35 +146,9 @@ let nextKey = 1;
 // arrival order into alternating slots, never more than two in flight, the older one collected before a third is submitted — the order proveMany always used
 // (submit0 submit1 collect0 submit0 collect1 ...) — so concurrent prove() calls pipeline by themselves (10.8 -> 9.5 ms per proof at 2^20) and proveMany is a loop over
 // the same queue. A lone request with nothing in flight takes the one-call path. A job that fails rejects its own promise only; the slot it held is free again.
-const pipeQueue = [];
-let pumping = false;
-function pipelined(job) {
-    return new Promise((resolve, reject) => {
-        pipeQueue.push(Object.assign(job, { resolve, reject }));
-        if (!pumping) { pumping = true; Promise.resolve().then(pump); }        // started behind the current turn: requests made in the same turn are all in the queue when it looks
-    });
-}
-async function pump() {
-    const flight = [];                                     // submitted, not collected: oldest first
-    try {
-        while (pipeQueue.length || flight.length) {
-            if (pipeQueue.length == 1 && !flight.length && pipeQueue[0].single) {
-                // a lone request with nothing in flight: the one-call path (zkmi_groth16_prove) — measured 4 ms faster per isolated proof than submit + collect from Node
-                // (11.1 against 15.2 ms at 2^20); requests that arrive meanwhile wait in the queue and pipeline from the next turn on
-                const job = pipeQueue.shift();
-                try { job.resolve(await job.single(job.curveId, job.key, job.witness, job.r, job.s)); } catch (e) { job.reject(e); }
-                continue;
-            }
-            if (pipeQueue.length && flight.length < 2) {
-                const job = pipeQueue.shift(), slot = flight.length ? 1 - flight[0].slot : 0;
-                try { await job.submit(job.key, job.witness, slot); flight.push({ job, slot }); } catch (e) { job.reject(e); }
-                continue;
-            }
-            const { job, slot } = flight.shift();
-            try { job.resolve(await job.collect(job.curveId, job.key, slot, job.r, job.s)); } catch (e) { job.reject(e); }
-        }
-    } finally { pumping = false; }
-}
+// The queue and its pump live in js/device_queue.js, shared with the PLONK and FFLONK provers (one holder of the device at a time, arrival order): Groth16 requests
+// that are adjacent in that order still share the two slots in exactly this way.
+const { pipelined } = require("./device_queue.js");
 
 function makeProver(snarkjs, options) {
     options = options || {};

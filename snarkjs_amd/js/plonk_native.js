@@ -226,8 +226,9 @@ function prove(zkey, wtns, blindingMont = null, options = null) {
 // The reference's plonk16Prove is async (src/plonk_prove.js:47): here every wait of the round driver — the commitments of a round, the queued
 // transforms before a read-back — runs on a libuv pool thread (addon.msmTableMultiDevAsync / synchronizeAsync); what is left on the main thread
 // between two awaits only enqueues kernels (tens of microseconds per call). Same result as prove() for the same blinding values. Calls are
-// serialised per process (one device context, pipeline slot 0): a second proveAsync waits for the first.
-let asyncQueue = Promise.resolve();
+// serialised per process (one device context, pipeline slot 0) through js/device_queue.js, TOGETHER with the FFLONK and Groth16 provers: a round's commitments sit
+// in the slot's host state between their enqueue and their collect, and the event loop turns in between.
+const { exclusive } = require("./device_queue.js");
 function proveAsync(zkey, wtns, blindingMont = null, options = null) {
     const run = async () => {
         const key = zkey instanceof PlonkKey ? zkey : new PlonkKey(zkey, options);
@@ -249,9 +250,7 @@ function proveAsync(zkey, wtns, blindingMont = null, options = null) {
             if (!(zkey instanceof PlonkKey)) key.release();
         }
     };
-    const p = asyncQueue.then(run, run);
-    asyncQueue = p.catch(() => {});
-    return p;
+    return exclusive(run);
 }
 
 // Throughput mode: one proof per witness against one key, TWO in flight from this one thread. Every proof is a generator (proveSteps) that
@@ -276,14 +275,19 @@ function proveMany(zkey, wtnsList, blindingMonts = null, options = null) {
             for (const ent of live.slice()) {
                 call("zkmi_pipeline_select", ent.slot);
                 // the blocking call this proof stopped in front of (a round's commitments were ENQUEUED when it stopped: collected here), then on to its next one
-                const s = ent.steps.next(ent.pending ? commitCollect(key, ent.pending) : undefined);
-                ent.pending = null;
+                const waiting = ent.pending;
+                ent.pending = null;                                   // consumed by the collect below even when the proof then fails: the clean-up must not collect it again
+                const s = ent.steps.next(waiting ? commitCollect(key, waiting) : undefined);
                 if (s.done) { out[ent.idx] = s.value; finish(ent); } else if (s.value && s.value.commit) ent.pending = commitEnqueue(key, s.value.commit);
             }
         }
     } finally {
         for (const ent of live.slice()) {                  // an error in one proof: drop the other one too, leave no queued work behind
-            try { call("zkmi_pipeline_select", ent.slot); ent.steps.return(); call("zkmi_synchronize"); ent.polys.forEach((p) => p.free()); } catch (e) { /* already failing */ }
+            try {
+                call("zkmi_pipeline_select", ent.slot); ent.steps.return(); call("zkmi_synchronize");
+                if (ent.pending) commitCollect(key, ent.pending);       // commitments it had enqueued: collected into nothing, so that the slot does not stay busy (include/zkmi.h)
+            } catch (e) { /* already failing */ }
+            for (const p of ent.polys) { try { p.free(); } catch (e) { /* already failing */ } }      // whatever the clean-up above met
         }
         call("zkmi_pipeline_select", 0);
         if (!(zkey instanceof PlonkKey)) key.release();

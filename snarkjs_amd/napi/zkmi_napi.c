@@ -149,9 +149,17 @@ static int job_run(job_t* j) {
     switch (j->kind) {
     case 0: return zkmi_msm(j->curve, j->group, as_zk(&j->a), as_zk(&j->b), (size_t)j->n, (size_t)j->sb, (uint64_t)j->key, j->o0);
     case 1: return zkmi_ntt(j->curve, as_zk(&j->a), (uint8_t* const*)j->b.ptr, j->b.len, j->b.n, (unsigned)j->logn, j->inverse, j->has_first ? j->first : NULL, j->has_inc ? j->inc : NULL);
-    case 2: return zkmi_groth16_prove_paged(j->has_zk ? &j->zk->z : NULL, (uint64_t)j->key, j->a.ptr[0], j->a.len[0], j->first, j->inc, j->o0, j->o1, j->o2);
-    case 3: return zkmi_groth16_submit((uint64_t)j->key, j->a.ptr[0], j->a.len[0], j->slot);
-    case 4: return zkmi_groth16_collect((uint64_t)j->key, j->slot, j->first, j->inc, j->o0, j->o1, j->o2);
+    case 2: case 3: case 4: {
+        /* These three leave pipeline slot 0 active. On a pool thread they can run between two calls of a synchronous prover on the main thread (js/plonk_native.js:
+         * proveMany alternates between the slots), which must find the slot it selected: the active slot is put back. */
+        const int prev = zkmi_pipeline_active();
+        const int rc = j->kind == 2 ? zkmi_groth16_prove_paged(j->has_zk ? &j->zk->z : NULL, (uint64_t)j->key, j->a.ptr[0], j->a.len[0], j->first, j->inc, j->o0, j->o1, j->o2)
+                     : j->kind == 3 ? zkmi_groth16_submit((uint64_t)j->key, j->a.ptr[0], j->a.len[0], j->slot)
+                                    : zkmi_groth16_collect((uint64_t)j->key, j->slot, j->first, j->inc, j->o0, j->o1, j->o2);
+        /* a failed select would overwrite the thread's error text of a failed call: only after a success is its own result reported */
+        if (rc) { const char* e = zkmi_last_error(); char keep[400]; snprintf(keep, sizeof keep, "%s", e ? e : ""); (void)zkmi_pipeline_select(prev); snprintf(j->err, sizeof j->err, "zkmi error %d: %s", rc, keep); return rc; }
+        return zkmi_pipeline_select(prev);
+    }
     case 5: return zkmi_groth16_load_paged(&j->zk->z, (uint64_t)j->key);
     case 8: return zkmi_groth16_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
     case 9: return zkmi_plonk_verify_batch((uint64_t)j->key, j->a.ptr[0], j->b.n ? j->b.ptr[0] : NULL, (uint32_t)j->sb, (size_t)j->n, (int8_t*)j->o0);
@@ -179,7 +187,7 @@ static void job_execute(napi_env env, void* data) {
     job_t* j = (job_t*)data;
     pthread_mutex_lock(&g_lock);
     j->rc = job_run(j);
-    if (j->rc) { const char* e = zkmi_last_error(); snprintf(j->err, sizeof j->err, "zkmi error %d: %s", j->rc, e ? e : ""); }   /* thread-local: read it here */
+    if (j->rc && !j->err[0]) { const char* e = zkmi_last_error(); snprintf(j->err, sizeof j->err, "zkmi error %d: %s", j->rc, e ? e : ""); }   /* thread-local: read it here */
     pthread_mutex_unlock(&g_lock);
 }
 static void job_complete(napi_env env, napi_status status, void* data) {

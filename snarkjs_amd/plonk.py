@@ -269,6 +269,21 @@ class _Transcript:
         return int.from_bytes(keccak256(b"".join(self.parts)), "big") % self.f.r
 
 
+class Enqueued:
+    """What a proof's coroutine yields while the commitments of a round are enqueued and not yet collected. The library refuses every other MSM in a pipeline slot that
+    holds such a call (include/zkmi.h, at zkmi_pipeline_select), so a driver that gives the proof up at this point collects — and so drops — them (run_many)."""
+
+    def __init__(self, table, count):
+        self.table, self.count = table, count
+
+    def drop(self):
+        L = zkmi.lib()
+        curve, group = C.c_int(0), C.c_int(1)
+        L.zkmi_msm_table_info(self.table, C.byref(curve), C.byref(group), None)
+        out = np.zeros(self.count * 3 * group.value * (32 if curve.value == 0 else 48), np.uint8)
+        L.zkmi_msm_table_multi_collect(self.table, self.count, zkmi.ptr(out))        # into a buffer nobody reads; the slot's stream is idle already
+
+
 def _commit_enqueue(key, *polys):
     """Polynomial.multiExponentiation (polynomial.js:970-977) for the commitments of one round, first half: batchFromMontgomery and the MSMs over PTau[0:len] (resident table;
     the bucket reductions of the round share one set of launches) are ENQUEUED on the active pipeline slot (zkmi_msm_table_multi_enqueue_dev); nothing waits. r06: with two
@@ -335,23 +350,27 @@ def run_many(make_steps, n, in_flight=2):
     try:
         while nxt < n or live:
             while free and nxt < n:
-                live.append((free.pop(0), nxt, make_steps(nxt)))
+                live.append([free.pop(0), nxt, make_steps(nxt), None])
                 nxt += 1
             for ent in list(live):
-                slot, idx, steps = ent
+                slot, idx, steps, _ = ent
                 zkmi.check(L.zkmi_pipeline_select(slot))
+                ent[3] = None                          # what it had enqueued is collected first thing when it resumes, whether or not it then fails
                 try:
-                    next(steps)
+                    stopped = next(steps)
+                    ent[3] = stopped if isinstance(stopped, Enqueued) else None
                 except StopIteration as done:
                     out[idx] = done.value
                     live.remove(ent)
                     free.append(slot)
     finally:
-        for slot, _, steps in live:                    # an error in one proof: drop the other one too, leave no queued work behind
+        for slot, _, steps, enqueued in live:          # an error in one proof: drop the other one too, leave no queued work behind
             try:
                 L.zkmi_pipeline_select(slot)
                 steps.close()
                 L.zkmi_synchronize()
+                if enqueued is not None:               # the commitments it stopped behind: the slot must not stay busy
+                    enqueued.drop()
             except Exception:
                 pass
         L.zkmi_pipeline_select(0)
@@ -394,7 +413,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     d_int.free()                                                                          # stream-ordered: the gather above is the last reader
     (pA, eA), (pB, eB), (pC, eC) = A.ifft_blinded([b[2], b[1]]), B.ifft_blinded([b[4], b[3]]), Cw.ifft_blinded([b[6], b[5]])
     cm = _commit_enqueue(key, pA, pB, pC)
-    yield
+    yield Enqueued(key.ptau_table, cm[2])
     pts["A"], pts["B"], pts["C"] = _commit_collect(cm)
 
     # ---- ROUND 2 (:315-455)
@@ -413,7 +432,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
                                               zkmi.ptr(mont(gamma)), zkmi.ptr(mont(key.k1)), zkmi.ptr(mont(key.k2)), zkmi.ptr(w_n), Zb.ptr))
     pZ, eZ = Zb.ifft_blinded([b[9], b[8], b[7]])
     cm = _commit_enqueue(key, pZ)
-    yield
+    yield Enqueued(key.ptau_table, cm[2])
     pts["Z"], = _commit_collect(cm)
     if Zb.get(0) != 1:                                                                   # computeZ's check (:437-439), read behind the commitment's
         raise ValueError("Copy constraints does not match")                              # own wait: no extra bubble between the transforms and the MSM
@@ -437,7 +456,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     T1, T2, T3 = _Poly(f, n + 1, False), _Poly(f, n + 1, False), _Poly(f, n + 6, False)
     zkmi.check(L.zkmi_plonk_split_t_dev(f.cid, pT.ptr, 4 * n, n, zkmi.ptr(mont(b[10])), zkmi.ptr(mont(b[11])), T1.ptr, T2.ptr, T3.ptr))      # :649-672 in one launch
     cm = _commit_enqueue(key, T1, T2, T3)
-    yield
+    yield Enqueued(key.ptau_table, cm[2])
     pts["T1"], pts["T2"], pts["T3"] = _commit_collect(cm)
 
     # ---- ROUND 4 (:686-708)
@@ -489,7 +508,7 @@ def _prove_steps(zkey, witness_file, logger=None, options=None, blinding_mont=No
     Wxiw = lincomb(f, _Poly(f, pZ.n, False), [(pZ.ptr, pZ.n, None)], -ezw % r)
     zkmi.check(L.zkmi_poly_div_by_zerofier_enqueue(f.cid, Wxiw.ptr, Wxiw.n, 1, zkmi.ptr(mont(xiw))))
     cm = _commit_enqueue(key, Wxi, Wxiw)
-    yield
+    yield Enqueued(key.ptau_table, cm[2])
     pts["Wxi"], pts["Wxiw"] = _commit_collect(cm)
     if not (Wxi.tail_is_zero(Wxi.n - 1) and Wxiw.tail_is_zero(Wxiw.n - 1)):             # divByZerofier's test (polynomial.js:665-669), read behind the commitments' wait
         raise ValueError("Polynomial is not divisible")

@@ -41,6 +41,14 @@ def test_zkey_opened_by_offset_in_pages_and_shard_gaps():
     assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+@pytest.mark.skipif(NODE is None, reason="node is missing")
+def test_device_queue_order_sharing_and_release():
+    """js/device_queue.js alone with fake jobs (timers, no addon): arrival order, one holder of the device at a time, adjacent Groth16 requests share the two slots
+    in the order native_glue.js pins, a failed job releases the device and rejects only itself, a PLONK job behind two and ahead of 28 Groth16 jobs is not starved"""
+    r = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "device_queue_cpu.js")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
 @need_node
 @need_bundle
 def test_register_glue_against_reference_bundle():
