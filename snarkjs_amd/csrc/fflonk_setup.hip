@@ -1,120 +1,25 @@
 // snarkjs_amd/csrc/fflonk_setup.hip — host driver + C-ABI of the FFLONK setup (src/fflonk_setup.js) on the device.
 //
 // Host side, one serial pass over the r1cs constraint section: computeFFConstraints (:160-209) through src/r1cs_constraint_processor.js lowers every
-// constraint to rows [a, b, c, ql, qr, qm, qo, qc]. It is NOT the lowering of plonk_setup.hip: zero coefficients leave a combination before it is
-// classified and after a join, the selector columns stand in another order, and the domain keeps two rows free. The pass also notes, per position of
-// the permutation, which position visited the same signal last (writeSigma :340-415), as plonk_setup.hip does, so that k_psetup_sigma serves unchanged.
+// constraint to rows [a, b, c, ql, qr, qm, qo, qc]. The pass also notes, per position of the permutation, which position visited the same signal last
+// (writeSigma :340-415), so that k_psetup_sigma serves unchanged.
 // Device side: the kernels of plonk_setup.cuh and the library's transforms for sections 7 - 15, k_fsetup_c0 for section 17 and the MSM scalars, one MSM.
-#include <string.h>
-#include <algorithm>
+// The lowering and the device steps up to writeP4 are gate_setup.hpp's, shared with plonk_setup.hip; here are FFLONK's rules for them (FFLONK_RULES:
+// where it is NOT the lowering of PLONK), its curve policy, its checks, C0 with its commitment and the entry points.
 #include <chrono>
-#include <vector>
 #include "fflonk_setup.cuh"
-#include "host_field.hpp"
-#include "plonk_setup.cuh"
-#include "setup_common.hpp"
+#include "gate_setup.hpp"
 #include "zkmi_common.hpp"
 
 namespace zkmi {
 
 namespace {
 
-typedef host::HField<4> HF;
-typedef host::HFp<4> E;
-
-struct Lowered {
-    uint32_t n_vars = 0;                          // settings.nVars: grows with every addition
-    std::vector<uint32_t> add_sig;                // 2 per addition
-    std::vector<E> add_coef;                      // 2 per addition
-    std::vector<uint32_t> map[3];
-    std::vector<E> sel[5];                        // QL, QR, QM, QO, QC
-    uint32_t rows() const { return (uint32_t)map[0].size(); }
-};
-
-// cirPower of fflonk_setup.js:112: two rows of the domain stay free for the blinding coefficients
-int circuit_power(uint32_t rows) {
-    const int p = ref_log2(rows + 1) + 1;
-    return p < 3 ? 3 : p;
-}
-
-struct Lowering {
-    const HF F;
-    Lowered& L;
-    const E zero, one;
-    std::vector<Term> cs;                         // reduceCoefs' queue (shift from `head`, push at the back)
-    Lowering(const HF& f, Lowered& l) : F(f), L(l), zero(f.zero()), one(f.One()) {}
-
-    int row(uint32_t a, uint32_t b, uint32_t c, const E& ql, const E& qr, const E& qm, const E& qo, const E& qc) {
-        if (L.map[0].size() >= 0xfffffff0u) return fail(ZKMI_ERR_UNSUPPORTED, "fflonk_setup: more than 2^32 constraints");
-        L.map[0].push_back(a); L.map[1].push_back(b); L.map[2].push_back(c);
-        L.sel[0].push_back(ql); L.sel[1].push_back(qr); L.sel[2].push_back(qm); L.sel[3].push_back(qo); L.sel[4].push_back(qc);
-        return ZKMI_OK;
-    }
-    // normalizeLinearCombination (r1cs_constraint_processor.js:86-93): Fr.isZero reads the Montgomery bytes, so zero coefficients DO leave
-    static void normalize(Lc& lc) {
-        lc.erase(std::remove_if(lc.begin(), lc.end(), [](const Term& t) { return t.c.is_zero(); }), lc.end());
-    }
-    // getLinearCombinationType (:53-84) of a normalized combination; its own `== 0n` compares a byte array and never fires
-    static int type_of(const Lc& lc) {
-        for (const Term& t : lc) if (t.s != 0) return 2;
-        return lc.empty() ? 0 : 1;
-    }
-    // reduceCoefs (:118-160): folds from the FRONT, two entries leave, the new signal enters at the back with coefficient one (`!= 0n` never fires)
-    struct Reduced { E k; uint32_t s[3]; E c[3]; };
-    int reduce(const Lc& lc, size_t max_c, Reduced& out) {
-        out.k = zero;
-        cs.clear();
-        for (const Term& t : lc) { if (t.s == 0) out.k = t.c; else cs.push_back(t); }
-        size_t head = 0;
-        while (cs.size() - head > max_c) {
-            const Term c1 = cs[head], c2 = cs[head + 1];
-            head += 2;
-            if (L.n_vars == 0xffffffffu) return fail(ZKMI_ERR_UNSUPPORTED, "fflonk_setup: more than 2^32 signals");
-            const uint32_t so = L.n_vars++;
-            ZK_TRY(row(c1.s, c2.s, so, F.neg(c1.c), F.neg(c2.c), zero, one, zero));
-            L.add_sig.push_back(c1.s); L.add_sig.push_back(c2.s);
-            L.add_coef.push_back(c1.c); L.add_coef.push_back(c2.c);
-            cs.push_back(Term{so, one});
-        }
-        for (size_t i = 0; i < max_c; i++) {
-            if (head + i < cs.size()) { out.s[i] = cs[head + i].s; out.c[i] = cs[head + i].c; }
-            else { out.s[i] = 0; out.c[i] = zero; }
-        }
-        return ZKMI_OK;
-    }
-    int sum(const Lc& lc) {                       // processR1csAdditionConstraint (:162-175)
-        Reduced C;
-        ZK_TRY(reduce(lc, 3, C));
-        return row(C.s[0], C.s[1], C.s[2], C.c[0], C.c[1], zero, C.c[2], C.k);
-    }
-    int mul(const Lc& a, const Lc& b, const Lc& c) {          // processR1csMultiplicationConstraint (:177-196)
-        Reduced A, B, C;
-        ZK_TRY(reduce(a, 1, A));
-        ZK_TRY(reduce(b, 1, B));
-        ZK_TRY(reduce(c, 1, C));
-        return row(A.s[0], B.s[0], C.s[0], F.mul(A.c[0], B.k), F.mul(A.k, B.c[0]), F.mul(A.c[0], B.c[0]), F.neg(C.c[0]), F.sub(F.mul(A.k, B.k), C.k));
-    }
-    // joinLinearCombinations (:95-116): k * lc1 - lc2, keys ascending, terms that cancel leave
-    void join(const Lc& lc1, const E& k, const Lc& lc2, Lc& res) {
-        res.clear();
-        size_t i = 0, j = 0;
-        while (i < lc1.size() || j < lc2.size()) {
-            if (j == lc2.size() || (i < lc1.size() && lc1[i].s < lc2[j].s)) { res.push_back(Term{lc1[i].s, F.mul(k, lc1[i].c)}); i++; }
-            else if (i == lc1.size() || lc2[j].s < lc1[i].s) { res.push_back(Term{lc2[j].s, F.neg(lc2[j].c)}); j++; }
-            else { res.push_back(Term{lc1[i].s, F.add(F.mul(k, lc1[i].c), F.neg(lc2[j].c))}); i++; j++; }
-        }
-        normalize(res);
-    }
-    Lc joined;
-    int process(Lc& a, Lc& b, Lc& c) {            // processR1csConstraint (:32-51)
-        normalize(a); normalize(b); normalize(c);
-        const int ta = type_of(a), tb = type_of(b);
-        if (ta == 0 || tb == 0) return sum(c);
-        if (ta == 1) { join(b, a[0].c, c, joined); return sum(joined); }
-        if (tb == 1) { join(a, b[0].c, c, joined); return sum(joined); }
-        return mul(a, b, c);
-    }
-};
+// fflonk_setup.js with r1cs_constraint_processor.js. drop_zeros: normalizeLinearCombination (r1cs_constraint_processor.js:86-93) asks Fr.isZero, which
+// reads the Montgomery bytes, so zero coefficients leave a combination before it is classified (:32-51) and after a join (:95-116). free_rows: cirPower
+// is log2(rows + 1) + 1 (fflonk_setup.js:112), two rows of the domain stay free for the blinding coefficients, and writeSigma (:356-359) leaves them the
+// identity. sel_col: the rows are [.., ql, qr, qm, qo, qc] and sections 7 - 11 are QL QR QM QO QC.
+const GateRules FFLONK_RULES = {"fflonk_setup", true, 2, {0, 1, 2, 3, 4}};
 
 double g_fsetup_ms[4] = {0, 0, 0, 0};             // lowering (host), sigma, P4, C0 and its commitment: wall time of the last calls
 
@@ -125,129 +30,31 @@ int curve_check(int curve) {
     return ZKMI_OK;
 }
 
-int lower(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, Lowered& L) {
-    ZK_TRY(curve_check(curve));
-    const auto t0 = std::chrono::steady_clock::now();
-    const HF F = HF::from_cfg<Bn254Fr>();
-    // Deliberate deviation, the same as zkmi_plonk_setup_lower's: a file with nVars <= nPublic or a signal id beyond nVars is refused
-    if (n_vars <= n_public) return fail(ZKMI_ERR_INVALID, "fflonk_setup: nVars must exceed nPublic");
-    L.n_vars = n_vars;
-    Lowering lw(F, L);
-    for (uint32_t s = 1; s <= n_public; s++) ZK_TRY(lw.row(s, 0, 0, lw.one, lw.zero, lw.zero, lw.zero, lw.zero));      // getFFlonkConstantConstraint
-    PageReader rd(constraints);
-    Lc lc[3];
-    std::vector<Term> raw;
-    for (uint32_t c = 0; c < n_constraints; c++) {
-        for (int k = 0; k < 3; k++) ZK_TRY(read_lc(rd, F, n_vars, raw, lc[k], "fflonk_setup"));
-        ZK_TRY(lw.process(lc[0], lc[1], lc[2]));
-    }
-    if (L.rows() == 0) return fail(ZKMI_ERR_INVALID, "fflonk_setup: a circuit without constraints and without public signals");
-    g_fsetup_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ZKMI_OK;
-}
-
-// writeSigma's bookkeeping (:340-415) turned into one index per position: visit order is row by row, columns a, b, c; rows from the constraint count
-// up to domain - 3 hold signal 0; the last two rows keep the identity and belong to no signal's cycle
-void predecessors(const Lowered& L, uint32_t domain, uint32_t* pred) {
-    constexpr uint32_t NONE = 0xffffffffu;
-    std::vector<uint32_t> last(L.n_vars, NONE), first(L.n_vars, NONE);
-    const uint32_t rows = L.rows();
-    for (uint32_t i = 0; i < domain; i++)
-        for (uint32_t col = 0; col < 3; col++) {
-            const uint32_t p = col * domain + i;
-            if (i >= domain - 2) { pred[p] = p; continue; }              // rows <= domain - 2 (circuit_power)
-            const uint32_t s = i < rows ? L.map[col][i] : 0u;
-            if (last[s] == NONE) first[s] = p; else pred[p] = last[s];
-            last[s] = p;
-        }
-    for (uint32_t s = 0; s < L.n_vars; s++) if (first[s] != NONE) pred[first[s]] = last[s];     // a signal that never occurs: the reference's "Variable not used"
-}
-
-inline double ms_since(const std::chrono::steady_clock::time_point& t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
 template <class FqC, class FrC> int setup_run(const zkmi_fflonk_setup_in& in, const zkmi_fflonk_setup_out& out) {
     constexpr size_t sG1 = 2 * FqC::N * 4, sJ = 3 * FqC::N * 4;
-    constexpr int W = FrC::N;
-    Ctx& cx = ctx();
-    hipStream_t st = cx.stream;
-    const HF F = HF::from_cfg<FrC>();
-    const uint32_t D = in.domain_size, rows = in.n_constraints;
-    const size_t dom = D, n_poly = std::max<uint32_t>(in.n_public, 1u);
-    const unsigned lg = (unsigned)ref_log2(D);
+    const uint32_t D = in.domain_size;
+    const size_t dom = D;
+    hipStream_t st = ctx().stream;
     // deg C0 < 8n holds by construction (eight polynomials of n coefficients): the lengths are all there is to check
-    if (out.q_len != 5 * dom * 32 || out.sigma_len != 15 * dom * 32 || out.lagrange_len != n_poly * 5 * dom * 32 || out.c0_len != 8 * dom * 32 || out.commitment_len != sG1)
-        return fail(ZKMI_ERR_INVALID, "fflonk_setup: an output buffer does not have the length of its section");
-    for (int c = 0; c < 5; c++) if (!out.q[c]) return fail(ZKMI_ERR_INVALID, "fflonk_setup: null output buffer");
-    if (!out.sigma || !out.lagrange || !out.c0 || !out.commitment || !in.selectors || !in.pred) return fail(ZKMI_ERR_INVALID, "fflonk_setup: null buffer");
-    if (pages_bytes(in.tau_g1) != 8 * dom * sG1) return fail(ZKMI_ERR_INVALID, "fflonk_setup: the tauG1 slice does not hold 8 * domainSize points");
-    for (size_t p = 0; p < 3 * dom; p++) if (in.pred[p] >= 3 * dom) return fail(ZKMI_ERR_INVALID, "fflonk_setup: a predecessor index lies beyond the permutation");
-
-    // computeK1K2 (:513-532) never advances: Fr.add is called without an assignment, so it returns k1 = 2 and k2 = 3 or does not return at all
-    E w, firsts[3] = {F.One(), F.from_u64(2), F.from_u64(3)};
-    ZK_TRY(zkmi_fr_root(in.curve, lg, (uint8_t*)w.v));
-    const E w_inv = F.inv(w), n_inv = F.inv(F.from_u64(D));
-    Fp<FrC> one_dev;
-    for (int i = 0; i < W; i++) one_dev.l[i] = FrC::one(i);
-
-    DevMem dm("fflonk_setup");
-    uint32_t *d_sel, *d_pred, *d_ones, *d_ident, *d_cols, *d_sec, *d_lag, *d_c0, *d_sc, *d_pts;
-    ZK_TRY(dm.get((size_t)5 * rows * 32, (void**)&d_sel));
-    ZK_TRY(dm.get(3 * dom * 4, (void**)&d_pred));
-    ZK_TRY(dm.get(dom * 32, (void**)&d_ones));
-    ZK_TRY(dm.get(3 * dom * 32, (void**)&d_ident));
-    ZK_TRY(dm.get(8 * dom * 32, (void**)&d_cols));                       // QL QR QM QO QC S1 S2 S3: the evaluations on the domain
-    ZK_TRY(dm.get(8 * 5 * dom * 32, (void**)&d_sec));                    // sections 7 .. 14: n coefficients, 4n evaluations each
-    ZK_TRY(dm.get(n_poly * 5 * dom * 32, (void**)&d_lag));               // section 15
-    ZK_TRY(dm.get(8 * dom * 32, (void**)&d_c0));                         // section 17
-    ZK_TRY(dm.get(8 * dom * 32, (void**)&d_sc));                         // the same, canonical: the MSM's scalars
-    ZK_TRY(dm.get(8 * dom * sG1, (void**)&d_pts));
-    ZK_HIP(hipMemcpyAsync(d_sel, in.selectors, (size_t)5 * rows * 32, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(d_pred, in.pred, 3 * dom * 4, hipMemcpyHostToDevice, st));
-    ZK_TRY(upload_pages(in.tau_g1, 8 * dom * sG1, d_pts));
-    ZK_HIP(hipStreamSynchronize(st));
-    const auto blocks = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-
-    // ---- selectors and sigma
-    auto t0 = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL((k_psetup_pad<FrC>), blocks(5 * dom), dim3(256), 0, st, d_sel, d_cols, rows, D);
-    hipLaunchKernelGGL((k_psetup_fill<FrC>), blocks(dom), dim3(256), 0, st, d_ones, (uint64_t)dom, one_dev);
-    ZK_HIP(hipGetLastError());
-    for (int col = 0; col < 3; col++) ZK_TRY(zkmi_fr_batch_apply_key_dev(in.curve, d_ones, d_ident + (size_t)col * dom * W, dom, (const uint8_t*)firsts[col].v, (const uint8_t*)w.v));
-    hipLaunchKernelGGL((k_psetup_sigma<FrC>), blocks(3 * dom), dim3(256), 0, st, d_ident, d_pred, d_cols + 5 * dom * W, (uint64_t)(3 * dom));
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipStreamSynchronize(st));
-    g_fsetup_ms[1] = ms_since(t0);
-
-    // ---- Polynomial.fromEvaluations + Evaluations.fromPolynomial(4) for the eight columns, writeP4 for the Lagrange polynomials
-    t0 = std::chrono::steady_clock::now();
-    for (int c = 0; c < 8; c++) {
-        uint32_t* sec = d_sec + (size_t)c * 5 * dom * W;
-        ZK_TRY(zkmi_ntt_dev(in.curve, d_cols + (size_t)c * dom * W, sec, lg, 1, nullptr, nullptr));
-        ZK_TRY(zkmi_ntt_padded_dev(in.curve, sec, dom, sec + dom * W, lg + 2, 0));
-    }
-    // d_ident is free again: its first column becomes the table w^(-e) / n
-    ZK_TRY(zkmi_fr_batch_apply_key_dev(in.curve, d_ones, d_ident, dom, (const uint8_t*)n_inv.v, (const uint8_t*)w_inv.v));
-    hipLaunchKernelGGL((k_psetup_lagrange<FrC>), blocks(n_poly * dom), dim3(256), 0, st, d_ident, d_lag, (uint32_t)n_poly, D);
-    ZK_HIP(hipGetLastError());
-    for (size_t i = 0; i < n_poly; i++) {
-        uint32_t* rec = d_lag + i * 5 * dom * W;
-        ZK_TRY(zkmi_ntt_padded_dev(in.curve, rec, dom, rec + dom * W, lg + 2, 0));
-    }
-    ZK_HIP(hipStreamSynchronize(st));
-    g_fsetup_ms[2] = ms_since(t0);
+    if (out.c0_len != 8 * dom * 32 || out.commitment_len != sG1) return fail(ZKMI_ERR_INVALID, "fflonk_setup: an output buffer does not have the length of its section");
+    if (!out.c0 || !out.commitment) return fail(ZKMI_ERR_INVALID, "fflonk_setup: null buffer");
+    GateDevice<FqC, FrC> dev("fflonk_setup");
+    ZK_TRY(dev.run(in.curve, in.n_public, in.n_constraints, D, in.selectors, in.pred, out.q, out.q_len, out.sigma, out.sigma_len, out.lagrange, out.lagrange_len,
+                   in.tau_g1, 8 * dom, "the tauG1 slice does not hold 8 * domainSize points", g_fsetup_ms));
+    uint32_t *d_c0, *d_sc;
+    ZK_TRY(dev.dm.get(8 * dom * 32, (void**)&d_c0));                     // section 17
+    ZK_TRY(dev.dm.get(8 * dom * 32, (void**)&d_sc));                     // the same, canonical: the MSM's scalars
 
     // ---- C0 and its commitment: the bases are used once, so the plain MSM (one copy of the points) and no window table
-    t0 = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL((k_fsetup_c0<FrC>), blocks(8 * dom), dim3(256), 0, st, d_sec, d_c0, d_sc, D);
+    const auto t0 = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL((k_fsetup_c0<FrC>), dim3((unsigned)((8 * dom + 255) / 256)), dim3(256), 0, st, dev.d_sec, d_c0, d_sc, D);
     ZK_HIP(hipGetLastError());
     uint8_t jac[sJ];
-    ZK_TRY(zkmi_msm_dev(in.curve, 1, d_pts, d_sc, 8 * dom, 32, jac));
+    ZK_TRY(zkmi_msm_dev(in.curve, 1, dev.d_pts, d_sc, 8 * dom, 32, jac));
     ZK_TRY(zkmi_to_affine(in.curve, 1, jac, out.commitment));
     g_fsetup_ms[3] = ms_since(t0);
 
-    for (int c = 0; c < 5; c++) ZK_HIP(hipMemcpyAsync(out.q[c], d_sec + (size_t)c * 5 * dom * W, 5 * dom * 32, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipMemcpyAsync(out.sigma, d_sec + (size_t)5 * 5 * dom * W, 15 * dom * 32, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipMemcpyAsync(out.lagrange, d_lag, n_poly * 5 * dom * 32, hipMemcpyDeviceToHost, st));
+    ZK_TRY(dev.download(out.q, out.sigma, out.lagrange));
     ZK_HIP(hipMemcpyAsync(out.c0, d_c0, 8 * dom * 32, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
@@ -274,36 +81,13 @@ using namespace zkmi;
 extern "C" {
 
 int zkmi_fflonk_setup_lower_len(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, uint32_t* counts4) {
-    if (!counts4) return fail(ZKMI_ERR_INVALID, "fflonk_setup_lower_len: null result");
-    Lowered L;
-    ZK_TRY(lower(curve, constraints, n_constraints, n_vars, n_public, L));
-    counts4[0] = L.n_vars; counts4[1] = (uint32_t)(L.add_sig.size() / 2); counts4[2] = L.rows();
-    const int power = circuit_power(L.rows());
-    counts4[3] = power < 32 ? 1u << power : 0u;
-    return ZKMI_OK;
+    ZK_TRY(curve_check(curve));
+    return lower_len_body(FFLONK_RULES, HF::from_cfg<Bn254Fr>(), constraints, n_constraints, n_vars, n_public, counts4, g_fsetup_ms[0]);
 }
 
 int zkmi_fflonk_setup_lower(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint32_t n_public, const zkmi_plonk_lowered* out) {
     ZK_TRY(curve_check(curve));
-    if (!out || !out->map_a || !out->map_b || !out->map_c || !out->selectors || !out->pred || (out->n_additions && !out->additions))
-        return fail(ZKMI_ERR_INVALID, "fflonk_setup_lower: null buffer");
-    Lowered L;
-    ZK_TRY(lower(curve, constraints, n_constraints, n_vars, n_public, L));
-    const uint32_t rows = L.rows(), n_add = (uint32_t)(L.add_sig.size() / 2);
-    const int power = circuit_power(rows);
-    if (out->plonk_n_vars != L.n_vars || out->n_additions != n_add || out->n_constraints != rows || power >= 31 || out->domain_size != 1u << power)
-        return fail(ZKMI_ERR_INVALID, "fflonk_setup_lower: the counts do not match the constraints (zkmi_fflonk_setup_lower_len)");
-    for (uint32_t i = 0; i < n_add; i++) {
-        uint8_t* rec = out->additions + (size_t)i * 72;
-        memcpy(rec, &L.add_sig[2 * i], 8);
-        memcpy(rec + 8, L.add_coef[2 * i].v, 32);
-        memcpy(rec + 40, L.add_coef[2 * i + 1].v, 32);
-    }
-    uint32_t* const maps[3] = {out->map_a, out->map_b, out->map_c};
-    for (int k = 0; k < 3; k++) memcpy(maps[k], L.map[k].data(), (size_t)rows * 4);
-    for (int k = 0; k < 5; k++) memcpy(out->selectors + (size_t)k * rows * 32, L.sel[k].data(), (size_t)rows * 32);
-    predecessors(L, out->domain_size, out->pred);
-    return ZKMI_OK;
+    return lower_body(FFLONK_RULES, HF::from_cfg<Bn254Fr>(), constraints, n_constraints, n_vars, n_public, out, g_fsetup_ms[0]);
 }
 
 int zkmi_fflonk_setup(const zkmi_fflonk_setup_in* in, const zkmi_fflonk_setup_out* out) {

@@ -1,6 +1,7 @@
 // snarkjs_amd/csrc/setup_common.hpp — what the setups (groth16_setup.hip, plonk_setup.hip, fflonk_setup.hip) share on the host: the device memory of
 // one call, a sequential reader over a paged buffer (the r1cs constraint section), the byte total of a paged buffer and, for the two gate lowerings,
-// one linear combination of a constraint as the reference's reader leaves it.
+// one linear combination of a constraint as the reference's reader leaves it. The lowering itself and the device steps that plonk_setup.hip and
+// fflonk_setup.hip share are in gate_setup.hpp, which builds on this file.
 #pragma once
 #include <string.h>
 #include <algorithm>

@@ -10,26 +10,19 @@ sections in the order the reference writes them: 1, 3 - 17, 2.
 
 BLS12-381 is refused: the reference writes BN254's w3 and wr into such a key (tests/test_fflonk_bls_unsupported.py), so no proof exists under it.
 """
-import ctypes as C
 import struct
 
-import numpy as np
-
+from . import _gate_setup as gate
 from . import zkmi
-from .groth16_setup import CURVES, SetupError, _Source, assemble, log2, read_ptau_header, read_r1cs_header, read_sections
+from .groth16_setup import SetupError, _Source, log2, read_ptau_header, read_r1cs_header, read_sections
 
 PROTOCOL_ID = 10
-# computeK1K2 (src/fflonk_setup.js:513-532) calls Fr.add without assigning its result: it returns 2 and 3 or never returns
-K1, K2 = 2, 3
+K1, K2 = gate.K1, gate.K2
 BN128_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 # computeW3 (:534-542) and getOmegaCubicRoot (:552-557), both hard-coded for BN254
 W3_GENERATOR = 31624
 W3_EXPONENT = 3648040478639879203707734290876212514758060733402672390616367364429301415936 // 3    # its "order(r - 1)" is (r - 1) / 6
 WR_FIRST_ROOT = 467799165886069610036046866799264026481344299079011762026774533774345988080
-
-
-def _fr_mont(v):
-    return ((v << 256) % BN128_R).to_bytes(32, "little")
 
 
 def fr_root(i):
@@ -48,45 +41,21 @@ def circuit_power(n_rows):
 
 
 def lower(cv, hdr, constraints):
-    """zkmi_fflonk_setup_lower (host only, needs no device): dict plonk_n_vars (nVars of the header), n_additions, n_constraints, domain_size and
-    numpy arrays additions (section 3), map_a, map_b, map_c (sections 4 - 6), selectors (QL QR QM QO QC: 5 x n_constraints x 32, Montgomery),
-    pred (3 x domain_size)"""
+    """zkmi_fflonk_setup_lower (host only, needs no device): the record of _gate_setup.lower, selectors QL QR QM QO QC"""
     L = zkmi.lib()
-    n_public = hdr["nOutputs"] + hdr["nPubInputs"]
-    pg = zkmi.pages_of(constraints)
-    cnt = (C.c_uint32 * 4)()
-    zkmi.check(L.zkmi_fflonk_setup_lower_len(cv["id"], pg.pages, hdr["nConstraints"], hdr["nVars"], n_public, cnt))
-    n_vars, n_add, n_c, dom = list(cnt)
-    out = dict(plonk_n_vars=n_vars, n_additions=n_add, n_constraints=n_c, domain_size=dom,
-               additions=np.zeros(n_add * 72, np.uint8), map_a=np.zeros(n_c, np.uint32), map_b=np.zeros(n_c, np.uint32), map_c=np.zeros(n_c, np.uint32),
-               selectors=np.zeros(5 * n_c * 32, np.uint8), pred=np.zeros(3 * dom, np.uint32))
-    rec = zkmi.PlonkLowered(n_vars, n_add, n_c, dom, *[out[k].ctypes.data for k in ("additions", "map_a", "map_b", "map_c", "selectors", "pred")])
-    zkmi.check(L.zkmi_fflonk_setup_lower(cv["id"], pg.pages, hdr["nConstraints"], hdr["nVars"], n_public, C.byref(rec)))
-    return out
+    return gate.lower(cv, hdr, constraints, L.zkmi_fflonk_setup_lower_len, L.zkmi_fflonk_setup_lower)
 
 
 def device_sections(cv, n_public, low, tau_g1):
     """zkmi_fflonk_setup: dict q (five arrays: sections 7 - 11), sigma (sections 12 - 14, one after the other), lagrange (15), c0 (17),
     commitment (one G1 point) as numpy uint8. tau_g1: the first 8 * domain_size points of ptau section 2."""
-    zkmi.init()
-    dom, s_g1 = low["domain_size"], 2 * cv["n8q"]
-    hold = zkmi.pages_of(tau_g1)
-    din = zkmi.FflonkSetupIn(cv["id"], n_public, low["n_constraints"], dom, low["selectors"].ctypes.data, low["pred"].ctypes.data, hold.pages)
-    q = [np.zeros(5 * dom * 32, np.uint8) for _ in range(5)]
-    sigma, lag = np.zeros(15 * dom * 32, np.uint8), np.zeros(max(n_public, 1) * 5 * dom * 32, np.uint8)
-    c0, com = np.zeros(8 * dom * 32, np.uint8), np.zeros(s_g1, np.uint8)
-    dout = zkmi.FflonkSetupOut((C.c_void_p * 5)(*[a.ctypes.data for a in q]), sigma.ctypes.data, lag.ctypes.data, c0.ctypes.data, com.ctypes.data,
-                               q[0].size, sigma.size, lag.size, c0.size, com.size)
-    zkmi.check(zkmi.lib().zkmi_fflonk_setup(C.byref(din), C.byref(dout)))
-    return dict(q=q, sigma=sigma, lagrange=lag, c0=c0, commitment=com)
+    return gate.device_sections(cv, n_public, low, tau_g1, zkmi.FflonkSetupIn, zkmi.FflonkSetupOut, zkmi.lib().zkmi_fflonk_setup,
+                                [("c0", 8 * low["domain_size"] * 32), ("commitment", 2 * cv["n8q"])])
 
 
 def header_sections(cv, n_public, low, commitment, x_2):
     """sections 1 and 2 (writeZkeyHeader :279-283, writeFFlonkHeader :466-503)"""
-    q = next(k for k, c in CURVES.items() if c is cv)
-    sec2 = struct.pack("<I", cv["n8q"]) + q.to_bytes(cv["n8q"], "little") + struct.pack("<I", 32) + cv["r"].to_bytes(32, "little") + \
-        struct.pack("<IIIII", low["plonk_n_vars"], n_public, low["domain_size"], low["n_additions"], low["n_constraints"]) + \
-        _fr_mont(K1) + _fr_mont(K2) + b"".join(_fr_mont(w) for w in roots(log2(low["domain_size"]))) + x_2 + bytes(commitment)
+    sec2 = gate.section2_head(cv, n_public, low) + b"".join(gate.fr_mont(BN128_R, w) for w in roots(log2(low["domain_size"]))) + x_2 + bytes(commitment)
     return struct.pack("<I", PROTOCOL_ID), sec2
 
 
@@ -124,8 +93,7 @@ def lower_checked(sp, cv, r1, sr, hdr):
 
 
 def section_16_and_x2(ptau, sp, cv, domain_size):
-    s_g1, s_g2 = 2 * cv["n8q"], 4 * cv["n8q"]
-    return ptau.read(sp[2][0][0], (domain_size * 9 + 18) * s_g1), ptau.read(sp[3][0][0] + s_g2, s_g2)
+    return ptau.read(sp[2][0][0], (domain_size * 9 + 18) * 2 * cv["n8q"]), gate.read_x2(ptau, sp, cv)
 
 
 def setup(r1cs, ptau):
@@ -147,7 +115,5 @@ def setup(r1cs, ptau):
         ptau_f.close(); r1_f.close()
 
 
-def assemble_fflonk(sections):
-    """createBinFile("zkey", 1, 17) with the sections in the order fflonk.setup writes them: 1, 3 - 17, then the FFLONK header"""
-    data = assemble(sections)
-    return data[:8] + struct.pack("<I", len(sections)) + data[12:]
+# createBinFile("zkey", 1, 17) with the sections in the order fflonk.setup writes them: 1, 3 - 17, then the FFLONK header
+assemble_fflonk = gate.assemble_gate_zkey

@@ -7,30 +7,21 @@
 const path = require("path");
 const { readerOf, sectionTable } = require("./groth16_native.js");
 const { SetupRefusal } = require("./groth16_setup_native.js");
+const { bigToLe, u32, log2, readPtauHeader, readR1csHeader, zkeyWriter } = require("./gate_setup_io.js");
 
 const Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583n;
 const R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
 const N8Q = 32, SG1 = 64, SG2 = 128;
 
-function leToBig(b) { let v = 0n; for (let i = b.length - 1; i >= 0; i--) v = (v << 8n) | BigInt(b[i]); return v; }
-function bigToLe(v, n) { const o = new Uint8Array(n); for (let i = 0; i < n; i++) { o[i] = Number(v & 0xffn); v >>= 8n; } return o; }
-function u32(v) { const b = Buffer.alloc(4); b.writeUInt32LE(v >>> 0); return b; }
-function log2(v) { return v > 0 ? 31 - Math.clz32(v) : 0; }
 function powMod(b, e) { let r = 1n; b %= R; while (e > 0n) { if (e & 1n) r = r * b % R; b = b * b % R; e >>= 1n; } return r; }
 const mont = (v) => bigToLe((v << 256n) % R, 32);
 // Fr.w[i] of ffjavascript on BN254
 const frRoot = (i) => powMod(powMod(5n, (R - 1n) >> 28n), 1n << BigInt(28 - i));
 
-function ptauPrime(pt, sp) {
-    const h = pt.read(sp[1][0].pos, sp[1][0].len), hv = new DataView(h.buffer, h.byteOffset, h.byteLength);
-    const n8 = hv.getUint32(0, true);
-    return leToBig(h.subarray(4, 4 + n8));
-}
-
 // whether the ceremony is on bn128: every other curve stays with the reference (register.js)
 function isBn128(ptauSrc) {
     const pt = readerOf(ptauSrc);
-    try { return ptauPrime(pt, sectionTable(pt, "ptau")) === Q; } catch (e) { return false; } finally { pt.close(); }
+    try { return readPtauHeader(pt, sectionTable(pt, "ptau")).q === Q; } catch (e) { return false; } finally { pt.close(); }
 }
 
 function setup(r1csSrc, ptauSrc, options) {
@@ -42,14 +33,12 @@ function setup(r1csSrc, ptauSrc, options) {
     try {
         const sp = sectionTable(pt, "ptau");
         if (!sp[12]) throw new SetupRefusal("Powers of Tau is not well prepared. Section 12 missing.");
-        const q = ptauPrime(pt, sp);
+        const { q } = readPtauHeader(pt, sp);
         if (q !== Q && q !== 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaabn) throw new Error(`Curve not supported: ${q}`);
         const ptauR = q === Q ? R : 52435875175126190479447740508185965837690552500527637822603658699938581184513n;
         r1 = readerOf(r1csSrc);
         const sr = sectionTable(r1, "r1cs");
-        const rh = r1.read(sr[1][0].pos, sr[1][0].len), rv = new DataView(rh.buffer, rh.byteOffset, rh.byteLength);
-        const rn8 = rv.getUint32(0, true), prime = leToBig(rh.subarray(4, 4 + rn8));
-        const nVars = rv.getUint32(4 + rn8, true), nOutputs = rv.getUint32(8 + rn8, true), nPubInputs = rv.getUint32(12 + rn8, true), nConstraints = rv.getUint32(28 + rn8, true);
+        const { prime, nVars, nOutputs, nPubInputs, nConstraints } = readR1csHeader(r1, sr);
         const nPublic = nOutputs + nPubInputs;
         if (prime !== ptauR) throw new SetupRefusal("r1cs curve does not match powers of tau ceremony curve");
         if (q !== Q) throw new SetupRefusal("fflonk.setup is not supported on BLS12-381: the reference writes BN254's w3 and wr into the key, so no proof under it verifies");
@@ -67,8 +56,7 @@ function setup(r1csSrc, ptauSrc, options) {
         const w3 = powMod(31624n, 3648040478639879203707734290876212514758060733402672390616367364429301415936n / 3n), wr = powMod(467799165886069610036046866799264026481344299079011762026774533774345988080n, 1n << BigInt(28 - cirPower));
         const sec2 = Buffer.concat([u32(N8Q), bigToLe(Q, N8Q), u32(32), bigToLe(R, 32), u32(low.plonkNVars), u32(nPublic), u32(domainSize), u32(low.nAdditions),
                                     u32(low.nConstraints), mont(2n), mont(3n), mont(w3), mont(frRoot(2)), mont(frRoot(3)), mont(wr), pt.read(sp[3][0].pos + SG2, SG2), dev.commitment]);
-        const parts = [Buffer.from("zkey"), u32(1), u32(17)];
-        const sec = (id, body) => { const l = Buffer.alloc(8); l.writeBigUInt64LE(BigInt(body.length)); parts.push(u32(id), l, body); };
+        const key = zkeyWriter(17), sec = key.sec;
         const rec = 5 * domainSize * 32;
         sec(1, u32(10));
         sec(3, low.additions); sec(4, low.mapA); sec(5, low.mapB); sec(6, low.mapC);
@@ -76,7 +64,7 @@ function setup(r1csSrc, ptauSrc, options) {
         for (let i = 0; i < 3; i++) sec(12 + i, dev.sigma.subarray(i * rec, (i + 1) * rec));
         sec(15, dev.lagrange); sec(16, sec16); sec(17, dev.c0);
         sec(2, sec2);
-        return new Uint8Array(Buffer.concat(parts));
+        return key.bytes();
     } finally {
         pt.close();
         if (r1) r1.close();

@@ -7,6 +7,7 @@
 const path = require("path");
 const { readerOf, sectionTable } = require("./groth16_native.js");
 const { SetupRefusal } = require("./groth16_setup_native.js");
+const { bigToLe, u32, log2, readPtauHeader, readR1csHeader, zkeyWriter } = require("./gate_setup_io.js");
 
 const CURVES = [
     { name: "bn128", id: 0, n8q: 32,
@@ -17,11 +18,6 @@ const CURVES = [
       r: 52435875175126190479447740508185965837690552500527637822603658699938581184513n },
 ];
 
-function leToBig(b) { let v = 0n; for (let i = b.length - 1; i >= 0; i--) v = (v << 8n) | BigInt(b[i]); return v; }
-function bigToLe(v, n) { const o = new Uint8Array(n); for (let i = 0; i < n; i++) { o[i] = Number(v & 0xffn); v >>= 8n; } return o; }
-function u32(v) { const b = Buffer.alloc(4); b.writeUInt32LE(v >>> 0); return b; }
-function log2(v) { return v > 0 ? 31 - Math.clz32(v) : 0; }
-
 function setup(r1csSrc, ptauSrc, options) {
     options = options || {};
     const addon = options.addon || require(path.join(__dirname, "..", "napi", "zkmi_napi.node"));
@@ -30,16 +26,12 @@ function setup(r1csSrc, ptauSrc, options) {
     let r1;
     try {
         const sp = sectionTable(pt, "ptau");
-        const h = pt.read(sp[1][0].pos, sp[1][0].len), hv = new DataView(h.buffer, h.byteOffset, h.byteLength);
-        const n8 = hv.getUint32(0, true), q = leToBig(h.subarray(4, 4 + n8));
+        const { q, power } = readPtauHeader(pt, sp);
         const cv = CURVES.find((c) => c.q === q);
         if (!cv) throw new Error(`Curve not supported: ${q}`);
-        const power = hv.getUint32(4 + n8, true);
         r1 = readerOf(r1csSrc);
         const sr = sectionTable(r1, "r1cs");
-        const rh = r1.read(sr[1][0].pos, sr[1][0].len), rv = new DataView(rh.buffer, rh.byteOffset, rh.byteLength);
-        const rn8 = rv.getUint32(0, true), prime = leToBig(rh.subarray(4, 4 + rn8));
-        const nVars = rv.getUint32(4 + rn8, true), nOutputs = rv.getUint32(8 + rn8, true), nPubInputs = rv.getUint32(12 + rn8, true), nConstraints = rv.getUint32(28 + rn8, true);
+        const { n8: rn8, prime, nVars, nOutputs, nPubInputs, nConstraints } = readR1csHeader(r1, sr);
         const nPublic = nOutputs + nPubInputs, sG1 = 2 * cv.n8q, sG2 = 4 * cv.n8q;
         if (logger) logger.info("Reading r1cs");
         // the reference lowers the constraints before it compares the curves (:62-72); a field of another width cannot be lowered at all
@@ -56,14 +48,13 @@ function setup(r1csSrc, ptauSrc, options) {
         const mont = (v) => bigToLe((v << 256n) % cv.r, 32);
         const sec2 = Buffer.concat([u32(cv.n8q), bigToLe(cv.q, cv.n8q), u32(32), bigToLe(cv.r, 32), u32(low.plonkNVars), u32(nPublic), u32(domainSize), u32(low.nAdditions),
                                     u32(low.nConstraints), mont(2n), mont(3n), dev.commitments, pt.read(sp[3][0].pos + sG2, sG2)]);
-        const parts = [Buffer.from("zkey"), u32(1), u32(14)];
-        const sec = (id, body) => { const l = Buffer.alloc(8); l.writeBigUInt64LE(BigInt(body.length)); parts.push(u32(id), l, body); };
+        const key = zkeyWriter(14), sec = key.sec;
         sec(3, low.additions); sec(4, low.mapA); sec(5, low.mapB); sec(6, low.mapC);
         for (let i = 0; i < 5; i++) sec(7 + i, dev.q[i]);
         sec(12, dev.sigma); sec(13, dev.lagrange);
         sec(14, pt.read(sp[2][0].pos, (domainSize + 6) * sG1));
         sec(1, u32(2)); sec(2, sec2);
-        return new Uint8Array(Buffer.concat(parts));
+        return key.bytes();
     } finally {
         pt.close();
         if (r1) r1.close();

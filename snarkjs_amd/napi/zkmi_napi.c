@@ -433,41 +433,64 @@ static napi_value js_plonk_setup_lower(napi_env env, napi_callback_info info) { 
 /* fflonkSetupLower(curve, nConstraints, nVars, nPublic, constraints): zkmi_fflonk_setup_lower (src/r1cs_constraint_processor.js; host only) -> the same
  * record as plonkSetupLower: plonkNVars is the header's nVars after the lowering, selectors are QL QR QM QO QC, pred is what fflonkSetup takes */
 static napi_value js_fflonk_setup_lower(napi_env env, napi_callback_info info) { return setup_lower(env, info, zkmi_fflonk_setup_lower_len, zkmi_fflonk_setup_lower); }
-/* plonkSetup(curve, nPublic, nConstraints, domainSize, selectors, pred, lagrangeG1): zkmi_plonk_setup -> {q: [5 sections 7 - 11], sigma, lagrange,
- * commitments}; selectors and pred as plonkSetupLower returned them (nConstraints = its PLONK constraints) */
-static napi_value js_plonk_setup(napi_env env, napi_callback_info info) {
+/* What plonkSetup and fflonkSetup share, as setup_lower serves the two lowering calls. gate_setup_begin: the seven arguments (curve, nPublic,
+ * nConstraints, domainSize, selectors, pred, points) with their checks, and the result object with q (five section buffers), sigma and lagrange.
+ * gate_setup_named: further output buffers as named properties. `oom` is the message thrown when a buffer cannot be allocated. */
+typedef struct gate_setup_front {
+    int32_t curve;
+    uint32_t n_public, n_constraints, domain_size;
+    const uint8_t* selectors;
+    const uint32_t* pred;
+    zkmi_pages points;
+    uint8_t *q[5], *sigma, *lagrange;
+    size_t q_len, sigma_len, lagrange_len;
+} gate_setup_front;
+static napi_value gate_setup_named(napi_env env, napi_value res, const char* oom, int n, const char* const* names, uint8_t** const* ptrs, const size_t* lens) {
+    for (int i = 0; i < n; i++) {
+        napi_value ta = new_u8(env, lens[i], ptrs[i]);
+        if (!ta) { napi_throw_error(env, NULL, oom); return NULL; }
+        NAPI_OK(napi_set_named_property(env, res, names[i], ta));
+    }
+    return res;
+}
+static napi_value gate_setup_begin(napi_env env, napi_callback_info info, const char* oom, gate_setup_front* f) {
     ARGS(7);
-    int32_t curve; double num[3];
+    double num[3];
     static pages_t pg[3];                  /* main thread only (a synchronous call) */
-    if (get_i32(env, argv[0], &curve) || (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381)) BAD_ARG();
+    if (get_i32(env, argv[0], &f->curve) || (f->curve != ZKMI_CURVE_BN128 && f->curve != ZKMI_CURVE_BLS12381)) BAD_ARG();
     for (int i = 0; i < 3; i++) if (get_f64(env, argv[1 + i], &num[i]) || num[i] < 0 || num[i] > 4294967295.0) BAD_ARG();
     for (int i = 0; i < 3; i++) if (get_pages(env, argv[4 + i], &pg[i])) BAD_ARG();
-    zkmi_plonk_setup_in in;
-    memset(&in, 0, sizeof in);
-    in.curve = curve; in.n_public = (uint32_t)num[0]; in.n_constraints = (uint32_t)num[1]; in.domain_size = (uint32_t)num[2];
-    if (pg[0].n != 1 || pg[1].n != 1 || pg[0].len[0] != (size_t)in.n_constraints * 160 || pg[1].len[0] != (size_t)in.domain_size * 12 || ((uintptr_t)pg[1].ptr[0] & 3)) BAD_ARG();
-    in.selectors = pg[0].ptr[0]; in.pred = (const uint32_t*)pg[1].ptr[0]; in.lagrange_g1 = as_zk(&pg[2]);
-    const size_t sG1 = curve == ZKMI_CURVE_BN128 ? 64 : 96, dom = in.domain_size, n_poly = in.n_public ? in.n_public : 1;
-    zkmi_plonk_setup_out out;
-    memset(&out, 0, sizeof out);
-    out.q_len = 5 * dom * 32; out.sigma_len = 15 * dom * 32; out.lagrange_len = n_poly * 5 * dom * 32; out.commitments_len = 8 * sG1;
+    f->n_public = (uint32_t)num[0]; f->n_constraints = (uint32_t)num[1]; f->domain_size = (uint32_t)num[2];
+    if (pg[0].n != 1 || pg[1].n != 1 || pg[0].len[0] != (size_t)f->n_constraints * 160 || pg[1].len[0] != (size_t)f->domain_size * 12 || ((uintptr_t)pg[1].ptr[0] & 3)) BAD_ARG();
+    f->selectors = pg[0].ptr[0]; f->pred = (const uint32_t*)pg[1].ptr[0]; f->points = as_zk(&pg[2]);
+    const size_t dom = f->domain_size, n_poly = f->n_public ? f->n_public : 1;
+    f->q_len = 5 * dom * 32; f->sigma_len = 15 * dom * 32; f->lagrange_len = n_poly * 5 * dom * 32;
     napi_value res, q;
     NAPI_OK(napi_create_object(env, &res));
     NAPI_OK(napi_create_array_with_length(env, 5, &q));
     for (int i = 0; i < 5; i++) {
-        napi_value ta = new_u8(env, out.q_len, &out.q[i]);
-        if (!ta) { napi_throw_error(env, NULL, "zkmi: plonkSetup: cannot allocate a section buffer"); return NULL; }
+        napi_value ta = new_u8(env, f->q_len, &f->q[i]);
+        if (!ta) { napi_throw_error(env, NULL, oom); return NULL; }
         NAPI_OK(napi_set_element(env, q, i, ta));
     }
     NAPI_OK(napi_set_named_property(env, res, "q", q));
-    static const char* names[3] = {"sigma", "lagrange", "commitments"};
-    uint8_t** ptrs[3] = {&out.sigma, &out.lagrange, &out.commitments};
-    const size_t lens[3] = {out.sigma_len, out.lagrange_len, out.commitments_len};
-    for (int i = 0; i < 3; i++) {
-        napi_value ta = new_u8(env, lens[i], ptrs[i]);
-        if (!ta) { napi_throw_error(env, NULL, "zkmi: plonkSetup: cannot allocate a section buffer"); return NULL; }
-        NAPI_OK(napi_set_named_property(env, res, names[i], ta));
-    }
+    static const char* names[2] = {"sigma", "lagrange"};
+    uint8_t** ptrs[2] = {&f->sigma, &f->lagrange};
+    const size_t lens[2] = {f->sigma_len, f->lagrange_len};
+    return gate_setup_named(env, res, oom, 2, names, ptrs, lens);
+}
+/* plonkSetup(curve, nPublic, nConstraints, domainSize, selectors, pred, lagrangeG1): zkmi_plonk_setup -> {q: [5 sections 7 - 11], sigma, lagrange,
+ * commitments}; selectors and pred as plonkSetupLower returned them (nConstraints = its PLONK constraints) */
+static napi_value js_plonk_setup(napi_env env, napi_callback_info info) {
+    static const char* oom = "zkmi: plonkSetup: cannot allocate a section buffer";
+    gate_setup_front f;
+    napi_value res = gate_setup_begin(env, info, oom, &f);
+    if (!res) return NULL;
+    const zkmi_plonk_setup_in in = {f.curve, f.n_public, f.n_constraints, f.domain_size, f.selectors, f.pred, f.points};
+    zkmi_plonk_setup_out out = {{f.q[0], f.q[1], f.q[2], f.q[3], f.q[4]}, f.sigma, f.lagrange, NULL, f.q_len, f.sigma_len, f.lagrange_len, 8 * (size_t)(f.curve == ZKMI_CURVE_BN128 ? 64 : 96)};
+    static const char* names[1] = {"commitments"};
+    uint8_t** ptrs[1] = {&out.commitments};
+    if (!gate_setup_named(env, res, oom, 1, names, ptrs, &out.commitments_len)) return NULL;
     int rc = ZK_CALL(zkmi_plonk_setup(&in, &out));
     if (rc) return throw_zkmi(env, rc);
     return res;
@@ -476,38 +499,16 @@ static napi_value js_plonk_setup(napi_env env, napi_callback_info info) {
  * one after the other), lagrange, c0, commitment}; selectors and pred as fflonkSetupLower returned them; tauG1 = the first 8 * domainSize points of ptau
  * section 2 */
 static napi_value js_fflonk_setup(napi_env env, napi_callback_info info) {
-    ARGS(7);
-    int32_t curve; double num[3];
-    static pages_t pg[3];                  /* main thread only (a synchronous call) */
-    if (get_i32(env, argv[0], &curve) || (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381)) BAD_ARG();
-    for (int i = 0; i < 3; i++) if (get_f64(env, argv[1 + i], &num[i]) || num[i] < 0 || num[i] > 4294967295.0) BAD_ARG();
-    for (int i = 0; i < 3; i++) if (get_pages(env, argv[4 + i], &pg[i])) BAD_ARG();
-    zkmi_fflonk_setup_in in;
-    memset(&in, 0, sizeof in);
-    in.curve = curve; in.n_public = (uint32_t)num[0]; in.n_constraints = (uint32_t)num[1]; in.domain_size = (uint32_t)num[2];
-    if (pg[0].n != 1 || pg[1].n != 1 || pg[0].len[0] != (size_t)in.n_constraints * 160 || pg[1].len[0] != (size_t)in.domain_size * 12 || ((uintptr_t)pg[1].ptr[0] & 3)) BAD_ARG();
-    in.selectors = pg[0].ptr[0]; in.pred = (const uint32_t*)pg[1].ptr[0]; in.tau_g1 = as_zk(&pg[2]);
-    const size_t dom = in.domain_size, n_poly = in.n_public ? in.n_public : 1;
-    zkmi_fflonk_setup_out out;
-    memset(&out, 0, sizeof out);
-    out.q_len = 5 * dom * 32; out.sigma_len = 15 * dom * 32; out.lagrange_len = n_poly * 5 * dom * 32; out.c0_len = 8 * dom * 32; out.commitment_len = 64;
-    napi_value res, q;
-    NAPI_OK(napi_create_object(env, &res));
-    NAPI_OK(napi_create_array_with_length(env, 5, &q));
-    for (int i = 0; i < 5; i++) {
-        napi_value ta = new_u8(env, out.q_len, &out.q[i]);
-        if (!ta) { napi_throw_error(env, NULL, "zkmi: fflonkSetup: cannot allocate a section buffer"); return NULL; }
-        NAPI_OK(napi_set_element(env, q, i, ta));
-    }
-    NAPI_OK(napi_set_named_property(env, res, "q", q));
-    static const char* names[4] = {"sigma", "lagrange", "c0", "commitment"};
-    uint8_t** ptrs[4] = {&out.sigma, &out.lagrange, &out.c0, &out.commitment};
-    const size_t lens[4] = {out.sigma_len, out.lagrange_len, out.c0_len, out.commitment_len};
-    for (int i = 0; i < 4; i++) {
-        napi_value ta = new_u8(env, lens[i], ptrs[i]);
-        if (!ta) { napi_throw_error(env, NULL, "zkmi: fflonkSetup: cannot allocate a section buffer"); return NULL; }
-        NAPI_OK(napi_set_named_property(env, res, names[i], ta));
-    }
+    static const char* oom = "zkmi: fflonkSetup: cannot allocate a section buffer";
+    gate_setup_front f;
+    napi_value res = gate_setup_begin(env, info, oom, &f);
+    if (!res) return NULL;
+    const zkmi_fflonk_setup_in in = {f.curve, f.n_public, f.n_constraints, f.domain_size, f.selectors, f.pred, f.points};
+    zkmi_fflonk_setup_out out = {{f.q[0], f.q[1], f.q[2], f.q[3], f.q[4]}, f.sigma, f.lagrange, NULL, NULL, f.q_len, f.sigma_len, f.lagrange_len, (size_t)f.domain_size * 8 * 32, 64};
+    static const char* names[2] = {"c0", "commitment"};
+    uint8_t** ptrs[2] = {&out.c0, &out.commitment};
+    const size_t lens[2] = {out.c0_len, out.commitment_len};
+    if (!gate_setup_named(env, res, oom, 2, names, ptrs, lens)) return NULL;
     int rc = ZK_CALL(zkmi_fflonk_setup(&in, &out));
     if (rc) return throw_zkmi(env, rc);
     return res;

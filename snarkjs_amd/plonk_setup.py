@@ -7,21 +7,14 @@ The gate lowering (sections 3 - 6, the selector columns, the permutation's prede
 kernels in csrc/plonk_setup.cuh). This module reads the slices of the two files that the reference reads (by offset: a large ptau is never loaded
 whole), writes the header sections 1 and 2 and the tauG1 copy of section 14, and puts the 14 sections in the order the reference writes them.
 """
-import ctypes as C
 import struct
 
-import numpy as np
-
+from . import _gate_setup as gate
 from . import zkmi
-from .groth16_setup import CURVES, SetupError, _Source, assemble, log2, read_ptau_header, read_r1cs_header, read_sections
+from .groth16_setup import SetupError, _Source, log2, read_ptau_header, read_r1cs_header, read_sections
 
 PROTOCOL_ID = 2
-# getK1K2 (src/plonk_setup.js:484-504) calls Fr.add without assigning its result: it returns 2 and 3 or never returns
-K1, K2 = 2, 3
-
-
-def _fr_mont(cv, v):
-    return ((v << 256) % cv["r"]).to_bytes(32, "little")
+K1, K2 = gate.K1, gate.K2
 
 
 def circuit_power(n_plonk_constraints):
@@ -30,42 +23,19 @@ def circuit_power(n_plonk_constraints):
 
 
 def lower(cv, hdr, constraints):
-    """zkmi_plonk_setup_lower (host only, needs no device): dict plonk_n_vars, n_additions, n_constraints, domain_size and numpy arrays
-    additions (section 3), map_a, map_b, map_c (sections 4 - 6), selectors (5 x n_constraints x 32, Montgomery), pred (3 x domain_size)"""
+    """zkmi_plonk_setup_lower (host only, needs no device): the record of _gate_setup.lower, selectors Qm Ql Qr Qo Qc"""
     L = zkmi.lib()
-    n_public = hdr["nOutputs"] + hdr["nPubInputs"]
-    pg = zkmi.pages_of(constraints)
-    cnt = (C.c_uint32 * 4)()
-    zkmi.check(L.zkmi_plonk_setup_lower_len(cv["id"], pg.pages, hdr["nConstraints"], hdr["nVars"], n_public, cnt))
-    n_vars, n_add, n_c, dom = list(cnt)
-    out = dict(plonk_n_vars=n_vars, n_additions=n_add, n_constraints=n_c, domain_size=dom,
-               additions=np.zeros(n_add * 72, np.uint8), map_a=np.zeros(n_c, np.uint32), map_b=np.zeros(n_c, np.uint32), map_c=np.zeros(n_c, np.uint32),
-               selectors=np.zeros(5 * n_c * 32, np.uint8), pred=np.zeros(3 * dom, np.uint32))
-    rec = zkmi.PlonkLowered(n_vars, n_add, n_c, dom, *[out[k].ctypes.data for k in ("additions", "map_a", "map_b", "map_c", "selectors", "pred")])
-    zkmi.check(L.zkmi_plonk_setup_lower(cv["id"], pg.pages, hdr["nConstraints"], hdr["nVars"], n_public, C.byref(rec)))
-    return out
+    return gate.lower(cv, hdr, constraints, L.zkmi_plonk_setup_lower_len, L.zkmi_plonk_setup_lower)
 
 
 def device_sections(cv, n_public, low, lagrange_g1):
     """zkmi_plonk_setup: dict q (five arrays: sections 7 - 11), sigma (12), lagrange (13), commitments (8 G1 points) as numpy uint8"""
-    zkmi.init()
-    dom, s_g1 = low["domain_size"], 2 * cv["n8q"]
-    hold = zkmi.pages_of(lagrange_g1)
-    din = zkmi.PlonkSetupIn(cv["id"], n_public, low["n_constraints"], dom, low["selectors"].ctypes.data, low["pred"].ctypes.data, hold.pages)
-    q = [np.zeros(5 * dom * 32, np.uint8) for _ in range(5)]
-    sigma, lag, com = np.zeros(15 * dom * 32, np.uint8), np.zeros(max(n_public, 1) * 5 * dom * 32, np.uint8), np.zeros(8 * s_g1, np.uint8)
-    dout = zkmi.PlonkSetupOut((C.c_void_p * 5)(*[a.ctypes.data for a in q]), sigma.ctypes.data, lag.ctypes.data, com.ctypes.data, q[0].size, sigma.size, lag.size, com.size)
-    zkmi.check(zkmi.lib().zkmi_plonk_setup(C.byref(din), C.byref(dout)))
-    return dict(q=q, sigma=sigma, lagrange=lag, commitments=com)
+    return gate.device_sections(cv, n_public, low, lagrange_g1, zkmi.PlonkSetupIn, zkmi.PlonkSetupOut, zkmi.lib().zkmi_plonk_setup, [("commitments", 8 * 2 * cv["n8q"])])
 
 
 def header_sections(cv, n_public, low, commitments, x_2):
     """sections 1 and 2 (writeHeaders, src/plonk_setup.js:436-482)"""
-    q = next(k for k, c in CURVES.items() if c is cv)
-    sec2 = struct.pack("<I", cv["n8q"]) + q.to_bytes(cv["n8q"], "little") + struct.pack("<I", 32) + cv["r"].to_bytes(32, "little") + \
-        struct.pack("<IIIII", low["plonk_n_vars"], n_public, low["domain_size"], low["n_additions"], low["n_constraints"]) + \
-        _fr_mont(cv, K1) + _fr_mont(cv, K2) + bytes(commitments) + x_2
-    return struct.pack("<I", PROTOCOL_ID), sec2
+    return struct.pack("<I", PROTOCOL_ID), gate.section2_head(cv, n_public, low) + bytes(commitments) + x_2
 
 
 def open_inputs(r1cs_src, ptau_src):
@@ -99,8 +69,7 @@ def lower_checked(ptau, sp, cv, power, r1, sr, hdr):
 
 
 def sections_14_and_x2(ptau, sp, cv, domain_size):
-    s_g1, s_g2 = 2 * cv["n8q"], 4 * cv["n8q"]
-    return ptau.read(sp[2][0][0], (domain_size + 6) * s_g1), ptau.read(sp[3][0][0] + s_g2, s_g2)
+    return ptau.read(sp[2][0][0], (domain_size + 6) * 2 * cv["n8q"]), gate.read_x2(ptau, sp, cv)
 
 
 def setup(r1cs, ptau):
@@ -120,7 +89,5 @@ def setup(r1cs, ptau):
         ptau_f.close(); r1_f.close()
 
 
-def assemble_plonk(sections):
-    """createBinFile("zkey", 1, 14) with the sections in the order plonk.setup writes them: 3 - 14, then the two headers"""
-    data = assemble(sections)
-    return data[:8] + struct.pack("<I", len(sections)) + data[12:]
+# createBinFile("zkey", 1, 14) with the sections in the order plonk.setup writes them: 3 - 14, then the two headers
+assemble_plonk = gate.assemble_gate_zkey

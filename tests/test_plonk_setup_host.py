@@ -143,7 +143,7 @@ def test_lowering_refuses_what_it_cannot_read():
 
 def test_deviations_from_the_reader_and_coefficients_of_r_or_more():
     """The reference's reader takes any 32 bytes (F.fromRprLE = toMontgomery of the raw value, which keeps c mod r); it does not compare nVars
-    with nPublic, which the lowering refuses on purpose (csrc/plonk_setup.hip: lower)"""
+    with nPublic, which the lowering refuses on purpose (csrc/gate_setup.hpp: lower)"""
     from snarkjs_amd.workloads import synth_r1cs
     for curve in ("bn128", "bls12381"):
         cv = next(c for c in gs.CURVES.values() if c["name"] == curve)
