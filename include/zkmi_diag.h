@@ -29,6 +29,40 @@ double zkmi_msm_accum_additions(int slot);
 /* Window width used for n terms (tuning knob; 0 restores the built-in table). */
 int zkmi_msm_set_window_bits(int c);
 
+/* The front half of an MSM on its own, for tests: runs the digit sort and the lane schedule the product runs (csrc/msm_sort.hip: msm_sort, the
+ * function behind every MSM entry point) over n device scalars of scalar_bytes bytes, waits for it, and copies what it built to the host.
+ *   precomp_c     0: no window table — c bits per window as zkmi_msm_dev picks them (zkmi_msm_set_window_bits, else the built-in table for n) and one
+ *                 set of buckets per window; 1..20: the lists of a window table built with that c (all windows share one set of buckets)
+ *   table_stride  points per table row (0: n); only read with a table
+ *   d_dropmask    optional device bitmap over the scalars, ceil(n / 32) words: a set bit leaves the scalar out of every list
+ * What the sort chose comes back in *info (always written once the sort has run). The flat bucket index is g = window * nb + magnitude - 1 (window = 0 with a
+ * table); a list entry is (table ? window * table_stride + i : i) | sign << 31 for scalar i.
+ * Every output array may be NULL (not copied); one that is given must hold at least the stated number of words or the call fails with
+ * ZKMI_ERR_INVALID — call once with NULL arrays to learn the sizes from *info:
+ *   counts, starts   info->total words each, counts_cap words of room each: entries per bucket, and where the bucket's list begins in sorted
+ *                    (the exclusive prefix sum of counts: the lists of all buckets form one flat array)
+ *   sorted           info->entries words, sorted_cap of room: the lists, bucket after bucket; the order inside a bucket is arbitrary
+ *   lane_g, lane_sub info->lanes words each, lanes_cap of room each: the bucket a lane of the accumulation works on, and which of the bucket's lanes it is
+ *   giants           3 * info->giants words, 3 * giants_cap of room: (bucket, first lane >> 7, lanes >> 7) of every bucket with more than 128 lanes
+ *   meta             3 words: all lanes, lanes of multi-lane buckets, giants
+ * Same entry rules as zkmi_msm_dev: needs a device, refused while the active pipeline slot holds work in flight. */
+typedef struct zkmi_msm_sort_info {
+    uint32_t c, Wd, W;          /* window bits; digit windows of a scalar; sets of buckets (Wd, or 1 with a table) */
+    uint32_t nb, total;         /* buckets per set = 2^(c-1); W * nb */
+    uint32_t cap;               /* list entries per lane the schedule aims at */
+    uint32_t nw;                /* 32-bit words of a scalar in the kernels instantiated for scalar_bytes: 1, 8 or 16 */
+    uint32_t radix;             /* 1: two-level LDS radix sort; 0: counting sort on global atomics (every field down to chunks is 0 then) */
+    uint32_t lb, parts;         /* radix: bits of the low key, and partitions = total >> lb */
+    uint32_t fused_cap;         /* radix: a partition of at most this many pairs is finished by the fused level 2; 0: every partition is cut into chunks */
+    uint32_t staged;            /* radix: 1 level-1 scatter ranked in LDS, 0 the direct scatter */
+    uint32_t chunks;            /* radix: chunks (of at most 8 192 pairs) the chunked level 2 worked through */
+    uint32_t entries;           /* list entries in all = non-zero digits of the scalars that were not dropped */
+    uint32_t lanes, giants;     /* meta[0], meta[2] */
+} zkmi_msm_sort_info;
+int zkmi_msm_sort_probe_dev(const void* d_scalars, size_t n, size_t scalar_bytes, int precomp_c, size_t table_stride, const uint32_t* d_dropmask,
+                            uint32_t* counts, uint32_t* starts, size_t counts_cap, uint32_t* sorted, size_t sorted_cap, uint32_t* lane_g, uint32_t* lane_sub,
+                            size_t lanes_cap, uint32_t* giants, size_t giants_cap, uint32_t* meta, zkmi_msm_sort_info* info);
+
 /* Device time (ms, HIP events) of the stages of the last proof, in order: buildABC, 6 NTTs, joinABC, sort(witness),
  * bucket accumulation of MSM B2, B1 (+ the second witness sort), A, C, sort(H scalars), accumulation of MSM H, batched G1 bucket reductions (the B2
  * reduction runs on a second stream underneath the G1 accumulations).

@@ -101,6 +101,15 @@ struct MsmPlan {
     size_t lane_bound = 0, multi_bound = 0;
     uint32_t *counts = nullptr, *starts = nullptr, *sorted = nullptr;
     uint32_t *lane_g = nullptr, *lane_sub = nullptr, *meta = nullptr, *giants = nullptr;
+    // which branch of the sort built the lists (host bookkeeping for zkmi_msm_sort_probe_dev; nothing on the device reads it): scalar words of the kernel
+    // instantiation; radix: lb low-key bits, parts partitions, fused_cap pairs a partition may hold for k_rsort_part (0: every partition is chunked),
+    // staged level-1 scatter or the direct one, and the chunk table's meta word (device: meta[0] = chunks cut by k_rsort_chunks)
+    struct Path {
+        int nw = 0;
+        bool radix = false, staged = false;
+        uint32_t lb = 0, parts = 0, fused_cap = 0;
+        const uint32_t* chunk_meta = nullptr;
+    } path;
 };
 constexpr int MSM_TB = 128, MSM_LOG_TB = 7;      // tree block: 128 lanes x 384 B (BLS12-381 G2 XYZZ) = 48 KiB of LDS
 // precomp_c != 0: the bases of every MSM run over this plan are pre-computed window tables built with that c

@@ -73,7 +73,7 @@ static uint32_t rsort_low_bits(const MsmShape& sh) {
     return RSORT_LOW_BITS;
 }
 template <int NW> static int msm_launch_digits_radix(const uint8_t* d_scalars, const MsmShape& sh, uint32_t* counts, uint32_t* starts, uint32_t* sorted,
-                                                     const uint32_t* dropmask, hipStream_t st, uint32_t* sched_zero, uint32_t sched_zero_words) {
+                                                     const uint32_t* dropmask, hipStream_t st, uint32_t* sched_zero, uint32_t sched_zero_words, MsmPlan::Path& path) {
     const uint32_t lb = rsort_fused_fits() ? rsort_low_bits(sh) : (uint32_t)RSORT_LOW_BITS;
     const uint32_t fused_cap = (lb < (uint32_t)RSORT_LOW_BITS) ? rsort_part_cap(lb) : 0u;
     const uint32_t total = (uint32_t)sh.W * sh.nb, P = total >> lb;
@@ -93,13 +93,15 @@ template <int NW> static int msm_launch_digits_radix(const uint8_t* d_scalars, c
     hipLaunchKernelGGL(k_msm_scan_sums, dim3(nsp), dim3(256), 0, st, bh, (uint32_t)nbh, part);
     hipLaunchKernelGGL(k_msm_scan_top, dim3(1), dim3(1024), 0, st, part, nsp);
     hipLaunchKernelGGL(k_msm_scan_final, dim3(nsp), dim3(256), 0, st, bh, (uint32_t)nbh, part, bhoff);
+    path.radix = true; path.lb = lb; path.parts = P; path.fused_cap = fused_cap; path.chunk_meta = meta;
     // level-1 scatter: ranked in LDS and written as runs where a block's pairs fit (ZKMI_RSORT_STAGED=0: the direct scatter everywhere)
     const uint32_t stage_cap = (uint32_t)sh.Wd * RSORT_TILE;
     const size_t stage_lds = ((size_t)2 * P + 1024 + (size_t)2 * stage_cap) * 4;
     // ... and where a block's share of a partition is long enough to be worth a run: >= 8 pairs on uniform scalars (26 at 2^20 terms with 512 partitions; with
     // thousands of partitions and 2 - 3 pairs per block and partition there is nothing to coalesce, and the staged kernel reads two entries of the scanned matrix per
     // partition where the direct one reads one)
-    if (rsort_staged_fits<NW>(stage_lds) && (size_t)stage_cap >= (size_t)8 * P)
+    path.staged = rsort_staged_fits<NW>(stage_lds) && (size_t)stage_cap >= (size_t)8 * P;
+    if (path.staged)
         hipLaunchKernelGGL((k_rsort_scatter1_staged<NW>), dim3(nblk), dim3(1024), stage_lds, st, d_scalars, sh, dropmask, P, lb, bhoff, stage_cap, tmp);
     else
         hipLaunchKernelGGL((k_rsort_scatter1<NW>), dim3(nblk), dim3(256), 0, st, d_scalars, sh, dropmask, P, lb, bhoff, tmp);
@@ -166,12 +168,14 @@ int msm_sort(const void* d_scalars, size_t n, size_t sb, MsmPlan& pl, int plan_s
     pl.meta = kcur + MSM_NKEYS; pl.giants = pl.meta + 8;
     const uint32_t sched_words = 3 * MSM_NKEYS + 8;                          // zeroed by the radix sort's chunk kernel on its way (one launch less), by a fill otherwise
     const uint8_t* sc = (const uint8_t*)d_scalars;
+    pl.path = MsmPlan::Path();
+    pl.path.nw = sb <= 4 ? 1 : sb <= 32 ? 8 : 16;
     uint32_t* part;
     ZK_TRY(ws_get("msm.scanpart" + sfx, (total / MSM_SCAN_CHUNK + 2) * 4, (void**)&part));
     if (msm_use_radix(sh)) {
-        if (sb <= 4) { ZK_TRY(msm_launch_digits_radix<1>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words)); }
-        else if (sb <= 32) { ZK_TRY(msm_launch_digits_radix<8>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words)); }
-        else { ZK_TRY(msm_launch_digits_radix<16>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words)); }
+        if (sb <= 4) { ZK_TRY(msm_launch_digits_radix<1>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words, pl.path)); }
+        else if (sb <= 32) { ZK_TRY(msm_launch_digits_radix<8>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words, pl.path)); }
+        else { ZK_TRY(msm_launch_digits_radix<16>(sc, sh, pl.counts, pl.starts, pl.sorted, d_dropmask, st, hist, sched_words, pl.path)); }
     } else {
     ZK_HIP(hipMemsetAsync(hist, 0, sched_words * 4, st));
     ZK_HIP(hipMemsetAsync(counts, 0, 3 * total * 4, st));

@@ -572,6 +572,45 @@ int zkmi_msm_dev(int curve, int group, const void* d_bases, const void* d_scalar
     if (n * pb > keep_limit) ws_drop("api.dev_bases29");
     return rc;
 }
+// The product's msm_sort on its own (include/zkmi_diag.h): plan slot 0 of the active pipeline slot, as msm_run / msm_run_table use it; then a wait and copies.
+int zkmi_msm_sort_probe_dev(const void* d_scalars, size_t n, size_t scalar_bytes, int precomp_c, size_t table_stride, const uint32_t* d_dropmask, uint32_t* counts,
+                            uint32_t* starts, size_t counts_cap, uint32_t* sorted, size_t sorted_cap, uint32_t* lane_g, uint32_t* lane_sub, size_t lanes_cap,
+                            uint32_t* giants, size_t giants_cap, uint32_t* meta, zkmi_msm_sort_info* info) {
+    ZK_TRY(require_ctx());
+    if (!d_scalars || !info) return fail(ZKMI_ERR_INVALID, "msm_sort_probe: null argument");
+    if (precomp_c < 0 || precomp_c > 20) return fail(ZKMI_ERR_INVALID, "msm_sort_probe: precomp_c must be 0 (no table) or 1..20");
+    if (table_stride && table_stride < n) return fail(ZKMI_ERR_INVALID, "msm_sort_probe: table_stride below n");
+    ZK_TRY(slot_idle_or_fail("msm_sort_probe"));
+    hipStream_t st = g_ctx.stream;
+    MsmPlan pl;
+    ZK_TRY(msm_sort(d_scalars, n, scalar_bytes, pl, 0, precomp_c, table_stride, d_dropmask));
+    ZK_HIP(hipStreamSynchronize(st));
+    const size_t total = pl.total;
+    uint32_t m[3] = {0, 0, 0}, last[2] = {0, 0}, chunks = 0;
+    ZK_HIP(hipMemcpy(m, pl.meta, sizeof m, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(&last[0], pl.counts + total - 1, 4, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(&last[1], pl.starts + total - 1, 4, hipMemcpyDeviceToHost));
+    if (pl.path.radix) ZK_HIP(hipMemcpy(&chunks, pl.path.chunk_meta, 4, hipMemcpyDeviceToHost));
+    const MsmShape& sh = pl.sh;
+    zkmi_msm_sort_info r = {};
+    r.c = (uint32_t)sh.c; r.Wd = (uint32_t)sh.Wd; r.W = (uint32_t)sh.W; r.nb = sh.nb; r.total = (uint32_t)total; r.cap = pl.cap; r.nw = (uint32_t)pl.path.nw;
+    r.radix = pl.path.radix; r.lb = pl.path.lb; r.parts = pl.path.parts; r.fused_cap = pl.path.fused_cap; r.staged = pl.path.staged; r.chunks = chunks;
+    r.entries = last[0] + last[1]; r.lanes = m[0]; r.giants = m[2];
+    *info = r;
+    // what the device wrote must fit the plan's own buffers before anything is copied out of them
+    if ((size_t)r.entries > (size_t)sh.Wd * n || (size_t)r.lanes > pl.lane_bound || (size_t)r.giants > pl.multi_bound / MSM_TB + 1)
+        return fail(ZKMI_ERR_INVALID, "msm_sort_probe: the sort reports more entries, lanes or giants than its buffers hold");
+    if (((counts || starts) && counts_cap < total) || (sorted && sorted_cap < r.entries) || ((lane_g || lane_sub) && lanes_cap < r.lanes) || (giants && giants_cap < r.giants))
+        return fail(ZKMI_ERR_INVALID, "msm_sort_probe: an output array is too small (sizes are in *info)");
+    if (counts) ZK_HIP(hipMemcpy(counts, pl.counts, total * 4, hipMemcpyDeviceToHost));
+    if (starts) ZK_HIP(hipMemcpy(starts, pl.starts, total * 4, hipMemcpyDeviceToHost));
+    if (sorted && r.entries) ZK_HIP(hipMemcpy(sorted, pl.sorted, (size_t)r.entries * 4, hipMemcpyDeviceToHost));
+    if (lane_g && r.lanes) ZK_HIP(hipMemcpy(lane_g, pl.lane_g, (size_t)r.lanes * 4, hipMemcpyDeviceToHost));
+    if (lane_sub && r.lanes) ZK_HIP(hipMemcpy(lane_sub, pl.lane_sub, (size_t)r.lanes * 4, hipMemcpyDeviceToHost));
+    if (giants && r.giants) ZK_HIP(hipMemcpy(giants, pl.giants, (size_t)r.giants * 12, hipMemcpyDeviceToHost));
+    if (meta) memcpy(meta, m, sizeof m);
+    return ZKMI_OK;
+}
 // ---- content-addressed cache of resident base tables behind zkmi_msm ---------------------------------------------------------
 // zkey sections and SRS slices are static, so the same bytes come back on every proof; their pre-computed window tables stay on
 // the device. The cache is keyed by the CONTENT of the base buffer — a 128-bit hash of every 64 KiB chunk, computed by the

@@ -779,10 +779,13 @@ def test_msm_sort_skewed_distributions(zk, dist, tables):
     assert np.array_equal(O.to_affine(c, group, out), want)
 
 
-@pytest.mark.parametrize("name,sb,lg", [("bn128", 4, 17), ("bn128", 48, 15), ("bls12381", 4, 16), ("bn128", 33, 15)])
+@pytest.mark.parametrize("name,sb,lg", [("bn128", 4, 17), ("bn128", 48, 15), ("bls12381", 4, 16), ("bn128", 33, 15), ("bn128", 48, 17), ("bn128", 33, 17)])
 def test_msm_scalar_widths_large(zk, name, sb, lg):
-    """Scalar widths other than 32 bytes on the large-input (LDS radix) sort path: 4-byte scalars (src/powersoftau_verify.js:371),
-    48-byte and odd-width scalars; values >= r are not reduced by the reference, the group does it. Closed form on geometric bases."""
+    """Scalar widths other than 32 bytes through zkmi_msm_dev at 2^15 terms and more: 4-byte scalars (src/powersoftau_verify.js:371), 48-byte and
+    odd-width scalars; values >= r are not reduced by the reference, the group does it. Closed form on geometric bases. Which sort each case takes
+    (csrc/msm_sort.hip: the LDS radix sort needs c > 11 and Wd * n >= 2^17; tests/test_gpu_msm_sort.py pins the rules): the two 4-byte cases take the
+    radix sort with one-word scalars (c = 15 and 12: 3 digits); the 48- and 33-byte cases at 2^15 terms get c = 11 from msm_pick_c and so the counting
+    sort, with 16-word scalars; at 2^17 terms c = 15 and both run the 16-word radix kernels, the 33-byte one through the byte-wise scalar load."""
     from snarkjs_amd import zkmi
     c, L = O.CURVE_ID[name], zkmi.lib()
     n = 1 << lg
