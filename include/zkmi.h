@@ -531,6 +531,21 @@ int zkmi_group_fft_dev(int curve, int group, const void* d_in, void* d_out, unsi
 int zkmi_group_batch_apply_key(int curve, int group, zkmi_pages in, uint8_t* const* out_ptr, const size_t* out_len, int n_out_pages, size_t n,
                                const uint8_t* first, const uint8_t* inc);
 int zkmi_group_batch_apply_key_dev(int curve, int group, const void* d_in, void* d_out, size_t n, const uint8_t* first, const uint8_t* inc);
+/* out_i = k * P_i for ONE scalar k (a Montgomery Fr element, host pointer): what G.batchApplyKey(buff, k, 1) computes, the shape of phase 2 of a Groth16
+ * ceremony (src/zkey_contribute.js:90-92: sections L and H times 1 / delta). Affine in and out as above; d_out == d_in is allowed. group == 1 runs a kernel
+ * of its own (the scalar is recoded once on the host, every lane takes the same branches), group == 2 the general kernel with inc = 1.
+ * Refused while a pipeline slot holds work in flight. */
+int zkmi_group_scale(int curve, int group, zkmi_pages in, uint8_t* const* out_ptr, const size_t* out_len, int n_out_pages, size_t n, const uint8_t* k_mont);
+int zkmi_group_scale_dev(int curve, int group, const void* d_in, void* d_out, size_t n, const uint8_t* k_mont);
+
+/* ---- the host side of a Groth16 phase-2 contribution (src/zkey_contribute.js, src/zkey_beacon.js, src/keypair.js); none of it needs a device --------
+ * zkmi_phase2_key_from_seed: rng = ChaCha(seed8) (ffjavascript's: eight 32-bit seed words); prv_key = Fr.fromRng(rng) (32 bytes: the integer drawn is the
+ *   element's Montgomery form), g1_s = G1.toAffine(G1.fromRng(rng)), g1_sx = prv_key * g1_s (affine Montgomery, 2 n8q bytes each).
+ * zkmi_phase2_hash_to_g2: hashToG2(transcript) of src/keypair.js:24-36 for a 64-byte transcript hash, as an affine point (4 n8q bytes).
+ * zkmi_point_mul: out = k * P for one affine point (2 * group * n8q bytes, all-zero = infinity) and a Montgomery Fr element k, affine out. */
+int zkmi_phase2_key_from_seed(int curve, const uint32_t* seed8, uint8_t* prv_key, uint8_t* g1_s, uint8_t* g1_sx);
+int zkmi_phase2_hash_to_g2(int curve, const uint8_t* transcript64, uint8_t* g2_sp);
+int zkmi_point_mul(int curve, int group, const uint8_t* affine, const uint8_t* k_mont, uint8_t* out_affine);
 
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,

@@ -145,6 +145,9 @@ int zkmi_plonk_setup_phase_ms(double* out4);
 /* Wall time in ms of the last FFLONK setup, four values: the gate lowering on the host (the last zkmi_fflonk_setup_lower or _lower_len), then of the
  * last zkmi_fflonk_setup the selector padding and sigma, the transforms of the eight columns and the Lagrange section, the C0 kernel and its commitment. */
 int zkmi_fflonk_setup_phase_ms(double* out4);
+/* The digit stream zkmi_group_scale hands its kernel for the scalar k (Montgomery Fr): the non-adjacent form of k, most significant digit first, one
+ * digit (-1, 0, 1) per byte; digits holds at least 256 bytes, *n_digits receives the count (0 for k = 0). Host only, needs no device. */
+int zkmi_group_scale_recode(int curve, const uint8_t* k_mont, int8_t* digits, int* n_digits);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPhase2) uninstallPhase2(curve);            // unregister(snarkjs): contribute / beacon of registerAll(snarkjs, { phase2: true }), before the setup gives the namespace back
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
     if (curve && curve.__zkmiPlonkSetup) uninstallPlonkSetup(curve);    // and the one installed by registerAll(snarkjs, { plonkSetup: true })
     if (curve && curve.__zkmiFflonkSetup) uninstallFflonkSetup(curve);  // and by registerAll(snarkjs, { fflonkSetup: true })
@@ -208,6 +209,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.setup) out.setup = installSetup(snarkjs, options);
     if (options && options.plonkSetup) out.plonkSetup = installPlonkSetup(snarkjs, options);
     if (options && options.fflonkSetup) out.fflonkSetup = installFflonkSetup(snarkjs, options);
+    if (options && options.phase2) out.phase2 = installPhase2(snarkjs, options);
     return out;
 }
 
@@ -248,6 +250,65 @@ function uninstallSetup(snarkjs) {
     if (!snarkjs.__zkmiSetup) return;
     snarkjs.zKey = snarkjs.__zkmiSetup.orig;
     delete snarkjs.__zkmiSetup;
+}
+
+// ---- zKey.contribute / zKey.beacon on the device (opt-in: registerAll(snarkjs, { phase2: true })) ------------------------------------------------------
+// Through the patched curve methods a contribution feeds G.batchApplyKey 2^16 points at a time (src/mpc_applykey.js:29-51), an upload, a launch of the
+// general kernel and a download per chunk; here sections L and H are one call each of the one-scalar kernel (js/groth16_phase2_native.js). Replaced
+// through the writable PROPERTY snarkjs.zKey like newZKey: same arguments, the same draw of 64 bytes (globalThis.crypto.getRandomValues where the
+// reference's browser build uses it), same result: the contribution hash; beacon returns false with the reference's logger.error where it refuses.
+// Handed to the saved reference function: an empty entropy (the reference asks for one), a point section larger than one buffer, and a name whose
+// UTF-8 form overflows the one-byte length field.
+function installPhase2(snarkjs, options) {
+    if (snarkjs.__zkmiPhase2) return snarkjs.__zkmiPhase2;
+    const phase2N = require("./groth16_phase2_native.js");
+    const saved = { contribute: snarkjs.zKey.contribute, beacon: snarkjs.zKey.beacon };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const hex = (b) => Buffer.from(b).toString("hex");
+    function store(zkeyName, zkey, what) {
+        if (typeof zkeyName === "string") require("fs").writeFileSync(zkeyName, zkey);
+        else if (zkeyName && zkeyName.type === "file") require("fs").writeFileSync(zkeyName.fileName, zkey);
+        else if (zkeyName && zkeyName.type === "mem") zkeyName.data = zkey;
+        else throw new Error(what + ": expected a path or a fastfile descriptor for the new key");
+    }
+    async function contribute(zkeyNameOld, zkeyNameNew, name, entropy, logger) {
+        if (!entropy) return saved.contribute(zkeyNameOld, zkeyNameNew, name, entropy, logger);
+        let res;
+        try {
+            const random64 = new Uint8Array(64);
+            if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random64); else require("crypto").randomFillSync(random64);
+            res = phase2N.contribute(zkeyNameOld, name, entropy, { addon, random64 });
+        } catch (e) {
+            if (e instanceof phase2N.Phase2Refusal && e.handOver) return saved.contribute(zkeyNameOld, zkeyNameNew, name, entropy, logger);
+            if (e instanceof phase2N.Phase2Refusal) throw new Error(e.message);
+            throw e;
+        }
+        store(zkeyNameNew, res.zkey, "zKey.contribute");
+        if (logger) { logger.info("Circuit Hash: " + hex(res.csHash)); logger.info("Contribution Hash: " + hex(res.contributionHash)); }
+        return res.contributionHash;
+    }
+    async function beacon(zkeyNameOld, zkeyNameNew, name, beaconHashStr, numIterationsExp, logger) {
+        let res;
+        try { res = phase2N.beacon(zkeyNameOld, name, beaconHashStr, numIterationsExp, { addon }); } catch (e) {
+            if (e instanceof phase2N.Phase2Refusal && e.handOver) return saved.beacon(zkeyNameOld, zkeyNameNew, name, beaconHashStr, numIterationsExp, logger);
+            if (e instanceof phase2N.Phase2Refusal && e.throws) throw new Error(e.message);
+            if (e instanceof phase2N.Phase2Refusal) { if (logger) logger.error(e.message); return false; }
+            throw e;
+        }
+        store(zkeyNameNew, res.zkey, "zKey.beacon");
+        if (logger) logger.info("Contribution Hash: " + hex(res.contributionHash));
+        return res.contributionHash;
+    }
+    // the namespace object in place now may already be the setup's copy (installSetup): keep whatever it holds, replace these two alone
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, { contribute, beacon }));
+    snarkjs.__zkmiPhase2 = { saved };
+    return snarkjs.__zkmiPhase2;
+}
+function uninstallPhase2(snarkjs) {
+    if (!snarkjs.__zkmiPhase2) return;
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiPhase2.saved));
+    delete snarkjs.__zkmiPhase2;
 }
 
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
@@ -392,4 +453,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, loadAddon };

@@ -347,6 +347,18 @@ static napi_value js_group_apply_key(napi_env env, napi_callback_info info) {
     if (rc) return throw_zkmi(env, rc);
     return NULL;
 }
+/* groupScale(curve, group, in, out, n, k): out_i = k * P_i over affine points for one Montgomery scalar k (G.batchApplyKey(buff, k, 1)) */
+static napi_value js_group_scale(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    int32_t curve, group; double n;
+    pages_t in, out;
+    const uint8_t* k;
+    if (get_i32(env, argv[0], &curve) || get_i32(env, argv[1], &group) || get_pages(env, argv[2], &in) || get_pages(env, argv[3], &out) || get_f64(env, argv[4], &n) ||
+        get_opt32(env, argv[5], &k) || !k) BAD_ARG();
+    int rc = ZK_CALL(zkmi_group_scale(curve, group, as_zk(&in), (uint8_t* const*)out.ptr, out.len, out.n, (size_t)n, k));
+    if (rc) return throw_zkmi(env, rc);
+    return NULL;
+}
 /* groupConvert(curve, group, kind, in, out, n): G.batchLEMtoU (0) / batchUtoLEM (1) / batchLEMtoC (2) / batchCtoLEM (3) */
 static napi_value js_group_convert(napi_env env, napi_callback_info info) {
     ARGS(6);
@@ -1040,6 +1052,8 @@ static const struct { const char* name; const char* sig; } g_call_table[] = {
     {"zkmi_plonk_gather_wires_mont_dev", "i d i d i d d d i i d d d"}, {"zkmi_ntt_padded_dev", "i d i d i i"}, {"zkmi_poly_blind_tail_dev", "i d i b*4:32 i"},
     {"zkmi_poly_lincomb_dev", "i d i b*4:56 i B32"}, {"zkmi_poly_evaluate_multi_dev", "i b*4:8 b*4:8 b*4:32 i b*4:32"}, {"zkmi_poly_div_by_zerofier_enqueue", "i d i i b32"},
     {"zkmi_plonk_split_t_dev", "i d i i b32 b32 d d d"},
+    /* the host side of a Groth16 phase-2 contribution (js/groth16_phase2_native.js); point buffers are 2 * group * n8q bytes, checked here for BN254's size */
+    {"zkmi_phase2_key_from_seed", "i b32 b32 b64 b64"}, {"zkmi_phase2_hash_to_g2", "i b64 b128"}, {"zkmi_point_mul", "i i b64 b32 b64"},
 };
 static void* zk_lib_handle(void) {
     static void* h = NULL;
@@ -1288,7 +1302,7 @@ static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) { 
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
-        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
+        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
         {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},

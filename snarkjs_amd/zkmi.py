@@ -43,6 +43,7 @@ SYMBOLS = [
     "zkmi_groth16_setup_coeffs_len", "zkmi_groth16_setup_coeffs", "zkmi_groth16_setup", "zkmi_groth16_setup_phase_ms",
     "zkmi_plonk_setup_lower_len", "zkmi_plonk_setup_lower", "zkmi_plonk_setup", "zkmi_plonk_setup_phase_ms",
     "zkmi_fflonk_setup_lower_len", "zkmi_fflonk_setup_lower", "zkmi_fflonk_setup", "zkmi_fflonk_setup_phase_ms",
+    "zkmi_group_scale", "zkmi_group_scale_dev", "zkmi_group_scale_recode", "zkmi_phase2_key_from_seed", "zkmi_phase2_hash_to_g2", "zkmi_point_mul",
 ]
 
 
@@ -303,6 +304,12 @@ def lib():
     L.zkmi_fflonk_setup_lower.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkLowered)]
     L.zkmi_fflonk_setup.argtypes = [C.POINTER(FflonkSetupIn), C.POINTER(FflonkSetupOut)]
     L.zkmi_fflonk_setup_phase_ms.argtypes = [C.POINTER(C.c_double)]
+    L.zkmi_group_scale.argtypes = [C.c_int, C.c_int, Pages, C.POINTER(vp), C.POINTER(sz), C.c_int, sz, u8p]
+    L.zkmi_group_scale_dev.argtypes = [C.c_int, C.c_int, vp, vp, sz, u8p]
+    L.zkmi_group_scale_recode.argtypes = [C.c_int, u8p, vp, C.POINTER(C.c_int)]
+    L.zkmi_phase2_key_from_seed.argtypes = [C.c_int, C.POINTER(C.c_uint32), u8p, u8p, u8p]
+    L.zkmi_phase2_hash_to_g2.argtypes = [C.c_int, u8p, u8p]
+    L.zkmi_point_mul.argtypes = [C.c_int, C.c_int, u8p, u8p, u8p]
     _lib = _Locked(L)
     return _lib
 
