@@ -547,6 +547,32 @@ int zkmi_phase2_key_from_seed(int curve, const uint32_t* seed8, uint8_t* prv_key
 int zkmi_phase2_hash_to_g2(int curve, const uint8_t* transcript64, uint8_t* g2_sp);
 int zkmi_point_mul(int curve, int group, const uint8_t* affine, const uint8_t* k_mont, uint8_t* out_affine);
 
+/* ---- verification of a Groth16 phase-2 key (src/zkey_verify_frominit.js, src/zkey_verify_fromr1cs.js) --------------------------------
+ * The reference's generator by position. ChaCha(seed8) is ffjavascript's: the keystream in nextU32 order is word j = word j % 16 of block j / 16.
+ * zkmi_chacha_words_dev: d_out[j] = keystream word first_word + j for j < n_words (32-bit words; first_word need not be a multiple of 16).
+ * zkmi_chacha_fr_dev: the first n results of Fr.fromRng on a fresh ChaCha(seed8), as the raw 32-byte little-endian integers the reference keeps (the integer
+ *   drawn IS the Montgomery form). Attempt k of the generator is words 8k .. 8k + 7 (limb i = w[2i] << 32 | w[2i + 1]), masked to the bit length of r and
+ *   kept iff below r; output i is the i-th kept attempt. *words_consumed (may be NULL) = the position a sequential generator would be at after the n-th
+ *   draw. A pure function of (curve, seed8, n); d_out (device memory, n x 32 bytes) must be 16-byte aligned. */
+int zkmi_chacha_words_dev(const uint32_t seed8[8], uint64_t first_word, void* d_out, size_t n_words);
+int zkmi_chacha_fr_dev(int curve, const uint32_t seed8[8], void* d_out, size_t n, uint64_t* words_consumed);
+/* misc.sameRatio (src/misc.js:129-137) for n quadruples in one launch, one lane each: verdicts[i] = 1 iff e(g1s_i, g2sx_i) * e(-g1sx_i, g2s_i) == 1.
+ * Points are affine Montgomery bytes as they lie in a zkey (2 n8q per G1 point, 4 n8q per G2 point; host pointers). A quadruple with any of its four
+ * points at infinity (all-zero bytes) is 0 and pairs nothing, as in the reference. */
+int zkmi_same_ratio_batch(int curve, const uint8_t* g1s, const uint8_t* g1sx, const uint8_t* g2s, const uint8_t* g2sx, size_t n, int8_t* verdicts);
+/* The two sums of sectionHasSameRatio (src/zkey_verify_frominit.js:234-269) over two G1 sections of n affine points: out_a = sum s_i A_i,
+ * out_b = sum s_i B_i with s_i = keystream word i of ChaCha(seed8) as a 4-byte scalar; the scalars are made on the device once and serve both sums.
+ * The sums add, so the reference's chunks of 2^20 points are not observable. n == 0: both results are infinity (all-zero) and nothing else is done.
+ * The two sums of sameRatioH (:271-350) for domainSize = 2^power. Fr(x): x taken as a Montgomery element.
+ *   raw[0 .. domain - 2] = zkmi_chacha_fr_dev(seed8), raw[domain - 1] = 0
+ *   out_r1 = sum fromMontgomery(raw_i) * (tau[domain + i] - tau[i]); the last term has scalar zero and tau[2 domain - 1] is never read, so tau_g1
+ *            holds 2 domain - 1 points (all a ptau of the key's own power has)
+ *   out_r2 = sum t_i H_i over the domain points of section 9, t = fromMontgomery(fft(applyKey(raw, -2, Fr.w[power + 1])))
+ * power >= Fr.s (the reference's other branch: 2^28 on BN254) is refused with ZKMI_ERR_UNSUPPORTED.
+ * Results are Jacobian, 3 n8q bytes, as zkmi_msm_dev writes them. Both calls are refused while a pipeline slot holds work in flight. */
+int zkmi_phase2_section_ratio(int curve, zkmi_pages a, zkmi_pages b, size_t n, const uint32_t seed8[8], uint8_t* out_a, uint8_t* out_b);
+int zkmi_phase2_h_ratio(int curve, zkmi_pages tau_g1, zkmi_pages h, uint32_t power, const uint32_t seed8[8], uint8_t* out_r1, uint8_t* out_r2);
+
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,
  * src/powersoftau_verify.js:358, src/mpc_applykey.js:64-70, src/zkey_export_bellman.js:36-83, src/zkey_new.js:103-115,373).

@@ -148,6 +148,17 @@ int zkmi_fflonk_setup_phase_ms(double* out4);
 /* The digit stream zkmi_group_scale hands its kernel for the scalar k (Montgomery Fr): the non-adjacent form of k, most significant digit first, one
  * digit (-1, 0, 1) per byte; digits holds at least 256 bytes, *n_digits receives the count (0 for k = 0). Host only, needs no device. */
 int zkmi_group_scale_recode(int curve, const uint8_t* k_mont, int8_t* digits, int* n_digits);
+/* What the generator kernels of zkmi_chacha_words_dev / zkmi_chacha_fr_dev are held to (csrc/chacha.cuh, csrc/phase2_host.hpp). Host only, no device.
+ *   _block_host         the block function the kernels run, on the host: block (counter_hi << 64 | counter_lo) of the keystream, 16 words
+ *   _struct_words_host  the same words drawn from the sequential generator struct (the pinned restatement), its counter set to block first_word / 16
+ *   _fr_host            n sequential Fr.fromRng draws from that struct (32 bytes each) and the position it ends at
+ *   _fr_compact_host    the kernels' rule on the host: attempts through the block function, kept ones in order
+ * zkmi_chacha_set_round_blocks: keystream blocks per round of zkmi_chacha_fr_dev (0, the default: by the curve's keep rate); the result does not depend on it. */
+int zkmi_chacha_block_host(const uint32_t seed8[8], uint64_t counter_lo, uint64_t counter_hi, uint32_t* out16);
+int zkmi_chacha_struct_words_host(const uint32_t seed8[8], uint64_t first_word, uint32_t* out, size_t n_words);
+int zkmi_chacha_fr_host(int curve, const uint32_t seed8[8], uint8_t* out, size_t n, uint64_t* words_consumed);
+int zkmi_chacha_fr_compact_host(int curve, const uint32_t seed8[8], uint8_t* out, size_t n, uint64_t* words_consumed);
+int zkmi_chacha_set_round_blocks(size_t blocks);
 
 #ifdef __cplusplus
 }

@@ -160,4 +160,4 @@ function beacon(zkeySrc, name, beaconHashStr, numIterationsExp, options) {
     return apply(zkeySrc, name, seedFromBeacon(a.beaconHash, a.numIterationsExp), { type: 1, numIterationsExp: a.numIterationsExp, beaconHash: a.beaconHash }, options);
 }
 
-module.exports = { contribute, beacon, Phase2Refusal, parseMpcParams, serialiseMpcParams, seedFromEntropy, seedFromBeacon };
+module.exports = { contribute, beacon, Phase2Refusal, parseMpcParams, serialiseMpcParams, seedFromEntropy, seedFromBeacon, hashPubKey, lemToUHost, leToBig, MAX_SECTION };

@@ -122,4 +122,4 @@ function newZKey(r1csSrc, ptauSrc, options) {
     }
 }
 
-module.exports = { newZKey, hashHChunks, hashedHPoints, SetupRefusal };
+module.exports = { newZKey, hashHChunks, hashedHPoints, SetupRefusal, CURVES, generatorsLem };

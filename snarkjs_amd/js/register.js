@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPhase2Verify) uninstallPhase2Verify(curve);    // unregister(snarkjs): verifyFromInit / verifyFromR1cs of registerAll(snarkjs, { phase2Verify: true })
     if (curve && curve.__zkmiPhase2) uninstallPhase2(curve);            // unregister(snarkjs): contribute / beacon of registerAll(snarkjs, { phase2: true }), before the setup gives the namespace back
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
     if (curve && curve.__zkmiPlonkSetup) uninstallPlonkSetup(curve);    // and the one installed by registerAll(snarkjs, { plonkSetup: true })
@@ -210,6 +211,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.plonkSetup) out.plonkSetup = installPlonkSetup(snarkjs, options);
     if (options && options.fflonkSetup) out.fflonkSetup = installFflonkSetup(snarkjs, options);
     if (options && options.phase2) out.phase2 = installPhase2(snarkjs, options);
+    if (options && options.phase2Verify) out.phase2Verify = installPhase2Verify(snarkjs, options);
     return out;
 }
 
@@ -309,6 +311,40 @@ function uninstallPhase2(snarkjs) {
     if (!snarkjs.__zkmiPhase2) return;
     snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiPhase2.saved));
     delete snarkjs.__zkmiPhase2;
+}
+
+// ---- zKey.verifyFromInit / zKey.verifyFromR1cs on the device (opt-in: registerAll(snarkjs, { phase2Verify: true })) -----------------------------------
+// Through the patched curve methods the verification reaches the device in chunks of 2^20 points, an upload and a download each, and two of its loops not at
+// all: the H check draws domainSize - 1 field elements one at a time from a generator in JavaScript, and batchSubtract sends g1m_subAffine task lists straight
+// to the workers. Here the same-ratio checks of a key are one launch, and the two sums of the L and of the H check one call each
+// (js/groth16_phase2_verify_native.js). Same arguments, the same verdict, the same lines to console.log and the logger. Handed to the saved reference
+// function: a section beyond one 2^30-byte buffer, power >= Fr.s, inputs the readers do not take, and for verifyFromR1cs what the device newZKey leaves to it.
+function installPhase2Verify(snarkjs, options) {
+    if (snarkjs.__zkmiPhase2Verify) return snarkjs.__zkmiPhase2Verify;
+    const verifyN = require("./groth16_phase2_verify_native.js");
+    const saved = { verifyFromInit: snarkjs.zKey.verifyFromInit, verifyFromR1cs: snarkjs.zKey.verifyFromR1cs };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const run = (which) => async function (firstName, pTauFileName, zkeyFileName, logger) {
+        const log = (level, text) => { if (level === "log") console.log(text); else if (logger) logger[level](text); };
+        try {
+            const random64 = new Uint8Array(64);
+            if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random64); else require("crypto").randomFillSync(random64);
+            return await verifyN[which](firstName, pTauFileName, zkeyFileName, { addon, log, random64 });
+        } catch (e) {
+            if (e instanceof verifyN.Phase2Refusal && e.handOver) return saved[which](firstName, pTauFileName, zkeyFileName, logger);
+            if (e instanceof verifyN.Phase2Refusal) throw new Error(e.message);
+            throw e;
+        }
+    };
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, { verifyFromInit: run("verifyFromInit"), verifyFromR1cs: run("verifyFromR1cs") }));
+    snarkjs.__zkmiPhase2Verify = { saved };
+    return snarkjs.__zkmiPhase2Verify;
+}
+function uninstallPhase2Verify(snarkjs) {
+    if (!snarkjs.__zkmiPhase2Verify) return;
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiPhase2Verify.saved));
+    delete snarkjs.__zkmiPhase2Verify;
 }
 
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
@@ -453,4 +489,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, loadAddon };

@@ -359,6 +359,41 @@ static napi_value js_group_scale(napi_env env, napi_callback_info info) {
     if (rc) return throw_zkmi(env, rc);
     return NULL;
 }
+/* ---- verification of a Groth16 phase-2 key (js/groth16_phase2_verify_native.js). seed: Uint8Array(32) over the eight 32-bit seed words in memory order.
+ * sameRatioBatch(curve, g1s, g1sx, g2s, g2sx, n) -> Uint8Array(n) of 0 | 1; the point buffers must hold exactly n points of the curve's size */
+static int n8q_of_curve(int32_t curve) { return curve == ZKMI_CURVE_BN128 ? 32 : curve == ZKMI_CURVE_BLS12381 ? 48 : 0; }
+static napi_value js_same_ratio_batch(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    int32_t curve; double n;
+    pages_t p[4];
+    if (get_i32(env, argv[0], &curve) || get_f64(env, argv[5], &n) || n < 0 || n > 16777216.0 || !n8q_of_curve(curve)) BAD_ARG();
+    for (int i = 0; i < 4; i++)
+        if (get_pages(env, argv[1 + i], &p[i]) || p[i].n != 1 || p[i].len[0] != (size_t)n * (size_t)n8q_of_curve(curve) * (i < 2 ? 2 : 4)) BAD_ARG();
+    uint8_t* out;
+    napi_value res = new_u8(env, (size_t)n, &out);
+    if (!res) BAD_ARG();
+    int rc = ZK_CALL(zkmi_same_ratio_batch(curve, p[0].ptr[0], p[1].ptr[0], p[2].ptr[0], p[3].ptr[0], (size_t)n, (int8_t*)out));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
+/* phase2SectionRatio(curve, a, b, n, seed) / phase2HRatio(curve, tauG1, h, power, seed) -> Uint8Array(6 n8q): the two sums, Jacobian, one after the other */
+static napi_value phase2_ratio_common(napi_env env, napi_callback_info info, int h_ratio) {
+    ARGS(5);
+    int32_t curve; double n;
+    pages_t a, b, seed;
+    if (get_i32(env, argv[0], &curve) || get_pages(env, argv[1], &a) || get_pages(env, argv[2], &b) || get_f64(env, argv[3], &n) || n < 0 || n > 4294967295.0 ||
+        get_pages(env, argv[4], &seed) || seed.n != 1 || seed.len[0] != 32 || ((uintptr_t)seed.ptr[0] & 3) || !n8q_of_curve(curve)) BAD_ARG();
+    const size_t q3 = 3 * (size_t)n8q_of_curve(curve);
+    uint8_t* out;
+    napi_value res = new_u8(env, 2 * q3, &out);
+    if (!res) BAD_ARG();
+    int rc = h_ratio ? ZK_CALL(zkmi_phase2_h_ratio(curve, as_zk(&a), as_zk(&b), (uint32_t)n, (const uint32_t*)seed.ptr[0], out, out + q3))
+                     : ZK_CALL(zkmi_phase2_section_ratio(curve, as_zk(&a), as_zk(&b), (size_t)n, (const uint32_t*)seed.ptr[0], out, out + q3));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
+static napi_value js_phase2_section_ratio(napi_env env, napi_callback_info info) { return phase2_ratio_common(env, info, 0); }
+static napi_value js_phase2_h_ratio(napi_env env, napi_callback_info info) { return phase2_ratio_common(env, info, 1); }
 /* groupConvert(curve, group, kind, in, out, n): G.batchLEMtoU (0) / batchUtoLEM (1) / batchLEMtoC (2) / batchCtoLEM (3) */
 static napi_value js_group_convert(napi_env env, napi_callback_info info) {
     ARGS(6);
@@ -1054,6 +1089,10 @@ static const struct { const char* name; const char* sig; } g_call_table[] = {
     {"zkmi_plonk_split_t_dev", "i d i i b32 b32 d d d"},
     /* the host side of a Groth16 phase-2 contribution (js/groth16_phase2_native.js); point buffers are 2 * group * n8q bytes, checked here for BN254's size */
     {"zkmi_phase2_key_from_seed", "i b32 b32 b64 b64"}, {"zkmi_phase2_hash_to_g2", "i b64 b128"}, {"zkmi_point_mul", "i i b64 b32 b64"},
+    /* the reference's generator by position (csrc/chacha.cuh): seed, first word | curve, seed; device output */
+    {"zkmi_chacha_words_dev", "b32 i d i"}, {"zkmi_chacha_fr_dev", "i b32 d i B8"},
+    /* the sequential generator on the host (include/zkmi_diag.h): what tests put in the kernels' place */
+    {"zkmi_chacha_struct_words_host", "b32 i b*3:4 i"}, {"zkmi_chacha_fr_host", "i b32 b*3:32 i B8"},
 };
 static void* zk_lib_handle(void) {
     static void* h = NULL;
@@ -1302,7 +1341,7 @@ static napi_value js_fflonk_vk_release(napi_env env, napi_callback_info info) { 
 static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
-        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
+        {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
         {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},

@@ -44,6 +44,8 @@ SYMBOLS = [
     "zkmi_plonk_setup_lower_len", "zkmi_plonk_setup_lower", "zkmi_plonk_setup", "zkmi_plonk_setup_phase_ms",
     "zkmi_fflonk_setup_lower_len", "zkmi_fflonk_setup_lower", "zkmi_fflonk_setup", "zkmi_fflonk_setup_phase_ms",
     "zkmi_group_scale", "zkmi_group_scale_dev", "zkmi_group_scale_recode", "zkmi_phase2_key_from_seed", "zkmi_phase2_hash_to_g2", "zkmi_point_mul",
+    "zkmi_chacha_words_dev", "zkmi_chacha_fr_dev", "zkmi_same_ratio_batch", "zkmi_phase2_section_ratio", "zkmi_phase2_h_ratio",
+    "zkmi_chacha_block_host", "zkmi_chacha_struct_words_host", "zkmi_chacha_fr_host", "zkmi_chacha_fr_compact_host", "zkmi_chacha_set_round_blocks",
 ]
 
 
@@ -310,6 +312,17 @@ def lib():
     L.zkmi_phase2_key_from_seed.argtypes = [C.c_int, C.POINTER(C.c_uint32), u8p, u8p, u8p]
     L.zkmi_phase2_hash_to_g2.argtypes = [C.c_int, u8p, u8p]
     L.zkmi_point_mul.argtypes = [C.c_int, C.c_int, u8p, u8p, u8p]
+    seed = C.POINTER(C.c_uint32)
+    L.zkmi_chacha_words_dev.argtypes = [seed, C.c_uint64, vp, sz]
+    L.zkmi_chacha_fr_dev.argtypes = [C.c_int, seed, vp, sz, C.POINTER(C.c_uint64)]
+    L.zkmi_same_ratio_batch.argtypes = [C.c_int, u8p, u8p, u8p, u8p, sz, u8p]
+    L.zkmi_phase2_section_ratio.argtypes = [C.c_int, Pages, Pages, sz, seed, u8p, u8p]
+    L.zkmi_phase2_h_ratio.argtypes = [C.c_int, Pages, Pages, C.c_uint32, seed, u8p, u8p]
+    L.zkmi_chacha_block_host.argtypes = [seed, C.c_uint64, C.c_uint64, vp]
+    L.zkmi_chacha_struct_words_host.argtypes = [seed, C.c_uint64, vp, sz]
+    L.zkmi_chacha_fr_host.argtypes = [C.c_int, seed, u8p, sz, C.POINTER(C.c_uint64)]
+    L.zkmi_chacha_fr_compact_host.argtypes = [C.c_int, seed, u8p, sz, C.POINTER(C.c_uint64)]
+    L.zkmi_chacha_set_round_blocks.argtypes = [sz]
     _lib = _Locked(L)
     return _lib
 
