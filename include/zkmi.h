@@ -573,6 +573,31 @@ int zkmi_same_ratio_batch(int curve, const uint8_t* g1s, const uint8_t* g1sx, co
 int zkmi_phase2_section_ratio(int curve, zkmi_pages a, zkmi_pages b, size_t n, const uint32_t seed8[8], uint8_t* out_a, uint8_t* out_b);
 int zkmi_phase2_h_ratio(int curve, zkmi_pages tau_g1, zkmi_pages h, uint32_t power, const uint32_t seed8[8], uint8_t* out_r1, uint8_t* out_r2);
 
+/* ---- verification of a powers-of-tau file (src/powersoftau_verify.js) ---------------------------------------------------------------
+ * zkmi_ptau_section_check: everything powersOfTau.verify needs of one section, from one upload. `tau` holds n_tau affine LEM points of `group` (section
+ * 2, 3, 4 or 5); `lagrange` (NULL: the file has none) holds the 2^(top + 1) - 1 points of section 12, 13, 14 or 15, top = power + 1 for tauG1 and power
+ * otherwise; zero_last is 1 for tauG1 alone, whose section holds 2^top - 1 points.
+ *   u_out    the n_tau points in U form (zkmi_group_convert_dev), the bytes the reference hashes, into the caller's pages
+ *   r1, r2   processSection (:340-396): r1 = sum_{i < n_tau - 1} s_i P_i, r2 = sum_{i < n_tau - 1} s_i P_{i+1}, s_i = keystream word i of
+ *            ChaCha(pair_seed8) as a 4-byte scalar. The sums add, so the reference's chunks of 2^16 points and its extra scalar for the pair that
+ *            straddles two chunks are this same formula. n_tau <= 1: both are infinity (all-zero).
+ *   ladder   verifyLagrangeEvaluations (:398-491), only with `lagrange`: ladder[p] for p = 0 .. top is 1 iff
+ *            sum_{i < 2^p} w_i tau_i == sum_{i < 2^p} fft_p(w)_i L_{2^p - 1 + i}, w_i = keystream word i of ChaCha(ladder_seed8), the generator restarted
+ *            for every p. For p == top with zero_last, w_{2^p - 1} = 0 and tau_{2^p - 1} is never read. The left sides are running sums over the dyadic
+ *            segments [2^(p-1), 2^p) with 4-byte scalars, so the tau section is walked once; the right sides transform the words widened to 32-byte
+ *            normal-form elements (a transform is linear: the reference's batchToMontgomery / batchFromMontgomery pair drops out).
+ * top > Fr.s is refused with ZKMI_ERR_UNSUPPORTED (BN254: a power-28 tauG1 section). r1, r2 are Jacobian, 3 * group * n8q bytes. Refused while a pipeline
+ * slot holds work in flight.
+ * zkmi_blake2b512_resume: misc.fromPartialHash(partial216) (src/misc.js:89-127: the 128-byte block buffer, the eight 64-bit state words as pairs of 32-bit
+ * words, length - position in words 16 / 17, the position in the buffer in words 18 / 19), then .update(data).digest(). Host only, needs no device. */
+int zkmi_ptau_section_check(int curve, int group, zkmi_pages tau, size_t n_tau, const zkmi_pages* lagrange, uint32_t top, int zero_last,
+                            const uint32_t pair_seed8[8], const uint32_t ladder_seed8[8], uint8_t* const* u_out_ptr, const size_t* u_out_len,
+                            int n_u_pages, uint8_t* r1, uint8_t* r2, int8_t* ladder);
+int zkmi_blake2b512_resume(const uint8_t* partial216, const uint8_t* data, size_t len, uint8_t* out64);
+/* keypair.createPTauKey (src/keypair.js:61-74) up to its G2 halves, for a beacon contribution: rng = ChaCha(seed8); three Fr.fromRng (tau, alpha, beta:
+ * prv_keys, 3 x 32 bytes), then per key g1_s = G1.fromRng(rng) and g1_sx = prvKey * g1_s (3 x 2 n8q bytes each, affine Montgomery). Host only. */
+int zkmi_ptau_key_from_seed(int curve, const uint32_t seed8[8], uint8_t* prv_keys, uint8_t* g1_s, uint8_t* g1_sx);
+
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,
  * src/powersoftau_verify.js:358, src/mpc_applykey.js:64-70, src/zkey_export_bellman.js:36-83, src/zkey_new.js:103-115,373).

@@ -114,6 +114,20 @@ template <class FqC, class FrC> static int key_from_seed(int curve, const uint32
     point_mul_host(c.Fq, c.Fr, s, prv, g1_sx);
     return ZKMI_OK;
 }
+// keypair.createPTauKey without its G2 halves: three Fr.fromRng (tau, alpha, beta), then per key G1.fromRng on the same generator and the product
+template <class FqC, class FrC> static int ptau_key_from_seed(int curve, const uint32_t* seed, uint8_t* prv3, uint8_t* g1_s3, uint8_t* g1_sx3) {
+    const auto c = phase2_curve<FqC, FrC>(curve);
+    constexpr size_t sG1 = 2 * FqC::N * 4;
+    phase2::ChaCha rng(seed);
+    for (int i = 0; i < 3; i++) { const host::HFp<4> k = phase2::field_from_rng(c.Fr, rng); memcpy(prv3 + 32 * i, k.v, 32); }
+    uint8_t cof[64];
+    const int bits = hex_le_bytes(cofactor_hex(curve, 1), cof, sizeof cof);
+    for (int i = 0; i < 3; i++) {
+        put_affine(c.Fq, phase2::point_from_rng(c.Fq, c.b1(), cof, bits, rng), g1_s3 + sG1 * i);
+        point_mul_host(c.Fq, c.Fr, g1_s3 + sG1 * i, prv3 + 32 * i, g1_sx3 + sG1 * i);
+    }
+    return ZKMI_OK;
+}
 template <class FqC, class FrC> static int hash_to_g2(int curve, const uint8_t* transcript, uint8_t* out) {
     const auto c = phase2_curve<FqC, FrC>(curve);
     uint32_t seed[8];
@@ -168,6 +182,10 @@ int zkmi_group_scale_recode(int curve, const uint8_t* k_mont, int8_t* digits, in
 int zkmi_phase2_key_from_seed(int curve, const uint32_t* seed8, uint8_t* prv_key, uint8_t* g1_s, uint8_t* g1_sx) {
     if ((curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) || !seed8 || !prv_key || !g1_s || !g1_sx) return fail(ZKMI_ERR_INVALID, "phase2_key_from_seed: bad argument");
     return curve == ZKMI_CURVE_BN128 ? key_from_seed<Bn254Fq, Bn254Fr>(curve, seed8, prv_key, g1_s, g1_sx) : key_from_seed<Bls12381Fq, Bls12381Fr>(curve, seed8, prv_key, g1_s, g1_sx);
+}
+int zkmi_ptau_key_from_seed(int curve, const uint32_t* seed8, uint8_t* prv_keys, uint8_t* g1_s, uint8_t* g1_sx) {
+    if ((curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) || !seed8 || !prv_keys || !g1_s || !g1_sx) return fail(ZKMI_ERR_INVALID, "ptau_key_from_seed: bad argument");
+    return curve == ZKMI_CURVE_BN128 ? ptau_key_from_seed<Bn254Fq, Bn254Fr>(curve, seed8, prv_keys, g1_s, g1_sx) : ptau_key_from_seed<Bls12381Fq, Bls12381Fr>(curve, seed8, prv_keys, g1_s, g1_sx);
 }
 int zkmi_phase2_hash_to_g2(int curve, const uint8_t* transcript64, uint8_t* g2_sp) {
     if ((curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) || !transcript64 || !g2_sp) return fail(ZKMI_ERR_INVALID, "phase2_hash_to_g2: bad argument");

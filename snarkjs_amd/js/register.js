@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPtauVerify) uninstallPtauVerify(curve);            // unregister(snarkjs): powersOfTau.verify of registerAll(snarkjs, { ptauVerify: true })
     if (curve && curve.__zkmiPhase2Verify) uninstallPhase2Verify(curve);    // unregister(snarkjs): verifyFromInit / verifyFromR1cs of registerAll(snarkjs, { phase2Verify: true })
     if (curve && curve.__zkmiPhase2) uninstallPhase2(curve);            // unregister(snarkjs): contribute / beacon of registerAll(snarkjs, { phase2: true }), before the setup gives the namespace back
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
@@ -212,6 +213,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.fflonkSetup) out.fflonkSetup = installFflonkSetup(snarkjs, options);
     if (options && options.phase2) out.phase2 = installPhase2(snarkjs, options);
     if (options && options.phase2Verify) out.phase2Verify = installPhase2Verify(snarkjs, options);
+    if (options && options.ptauVerify) out.ptauVerify = installPtauVerify(snarkjs, options);
     return out;
 }
 
@@ -345,6 +347,39 @@ function uninstallPhase2Verify(snarkjs) {
     if (!snarkjs.__zkmiPhase2Verify) return;
     snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiPhase2Verify.saved));
     delete snarkjs.__zkmiPhase2Verify;
+}
+
+// ---- powersOfTau.verify on the device (opt-in: registerAll(snarkjs, { ptauVerify: true })) -----------------------------------------------------------------
+// Through the patched curve methods the check reaches the device in chunks of 2^16 points, an upload and a download each, with JavaScript loops over the
+// generator for every power of every section and one WASM pairing per sameRatio. Here a section is one call and all same-ratio checks one launch
+// (js/powersoftau_verify_native.js). Same argument, verdict and info / warn / error lines. Handed to the saved reference function: a section beyond one
+// 2^30-byte buffer, power + 1 > Fr.s, inputs the readers do not take.
+function installPtauVerify(snarkjs, options) {
+    if (snarkjs.__zkmiPtauVerify) return snarkjs.__zkmiPtauVerify;
+    const verifyN = require("./powersoftau_verify_native.js");
+    const saved = { verify: snarkjs.powersOfTau.verify };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    async function verify(tauFilename, logger) {
+        const log = (level, text) => { if (logger) logger[level](text); };
+        try {
+            const random32 = new Uint8Array(32);
+            if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random32); else require("crypto").randomFillSync(random32);
+            return await verifyN.verify(tauFilename, { addon, log, random32 });
+        } catch (e) {
+            if (e instanceof verifyN.PtauRefusal && e.handOver) return saved.verify(tauFilename, logger);
+            if (e instanceof verifyN.PtauRefusal) throw new Error(e.message);
+            throw e;
+        }
+    }
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, { verify }));
+    snarkjs.__zkmiPtauVerify = { saved };
+    return snarkjs.__zkmiPtauVerify;
+}
+function uninstallPtauVerify(snarkjs) {
+    if (!snarkjs.__zkmiPtauVerify) return;
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, snarkjs.__zkmiPtauVerify.saved));
+    delete snarkjs.__zkmiPtauVerify;
 }
 
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
@@ -489,4 +524,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, loadAddon };

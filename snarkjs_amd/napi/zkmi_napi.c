@@ -394,6 +394,46 @@ static napi_value phase2_ratio_common(napi_env env, napi_callback_info info, int
 }
 static napi_value js_phase2_section_ratio(napi_env env, napi_callback_info info) { return phase2_ratio_common(env, info, 0); }
 static napi_value js_phase2_h_ratio(napi_env env, napi_callback_info info) { return phase2_ratio_common(env, info, 1); }
+/* ---- verification of a powers-of-tau file (js/powersoftau_verify_native.js)
+ * ptauSectionCheck(curve, group, tau, nTau, lagrange | null, top, zeroLast, pairSeed, ladderSeed) -> Uint8Array: the nTau points in U form, then r1 and r2
+ * (Jacobian, 3 * group * n8q bytes each), then top + 1 ladder verdicts (0 | 1; left 0 without a Lagrange section). Seeds as for phase2SectionRatio. */
+static napi_value js_ptau_section_check(napi_env env, napi_callback_info info) {
+    ARGS(9);
+    int32_t curve, group, zero_last; double n, top;
+    pages_t tau, lag, s1, s2;
+    napi_valuetype lt;
+    NAPI_OK(napi_typeof(env, argv[4], &lt));
+    const bool has_lag = !(lt == napi_null || lt == napi_undefined);
+    if (get_i32(env, argv[0], &curve) || get_i32(env, argv[1], &group) || (group != 1 && group != 2) || get_pages(env, argv[2], &tau) || get_f64(env, argv[3], &n) || n < 0 ||
+        n > 2147483647.0 || (has_lag && get_pages(env, argv[4], &lag)) || get_f64(env, argv[5], &top) || top < 0 || top > 64 || get_i32(env, argv[6], &zero_last) ||
+        get_pages(env, argv[7], &s1) || s1.n != 1 || s1.len[0] != 32 || ((uintptr_t)s1.ptr[0] & 3) || get_pages(env, argv[8], &s2) || s2.n != 1 || s2.len[0] != 32 ||
+        ((uintptr_t)s2.ptr[0] & 3) || !n8q_of_curve(curve)) BAD_ARG();
+    const size_t sg = 2 * (size_t)group * (size_t)n8q_of_curve(curve), jac = sg / 2 * 3, ub = (size_t)n * sg;
+    uint8_t* out;
+    napi_value res = new_u8(env, ub + 2 * jac + (size_t)top + 1, &out);
+    if (!res) BAD_ARG();
+    memset(out + ub, 0, 2 * jac + (size_t)top + 1);
+    zkmi_pages zl;
+    if (has_lag) zl = as_zk(&lag);
+    uint8_t* up[1] = {out};
+    const size_t ul[1] = {ub};
+    int rc = ZK_CALL(zkmi_ptau_section_check(curve, group, as_zk(&tau), (size_t)n, has_lag ? &zl : NULL, (uint32_t)top, zero_last, (const uint32_t*)s1.ptr[0], (const uint32_t*)s2.ptr[0],
+                                             up, ul, 1, out + ub, out + ub + jac, (int8_t*)(out + ub + 2 * jac)));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
+/* blake2bResume(partial216, data) -> Uint8Array(64): misc.fromPartialHash(partial).update(data).digest() */
+static napi_value js_blake2b_resume(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    pages_t p, d;
+    if (get_pages(env, argv[0], &p) || p.n != 1 || p.len[0] != 216 || get_pages(env, argv[1], &d) || d.n != 1) BAD_ARG();
+    uint8_t* out;
+    napi_value res = new_u8(env, 64, &out);
+    if (!res) BAD_ARG();
+    int rc = ZK_CALL(zkmi_blake2b512_resume(p.ptr[0], d.len[0] ? d.ptr[0] : NULL, d.len[0], out));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* groupConvert(curve, group, kind, in, out, n): G.batchLEMtoU (0) / batchUtoLEM (1) / batchLEMtoC (2) / batchCtoLEM (3) */
 static napi_value js_group_convert(napi_env env, napi_callback_info info) {
     ARGS(6);
@@ -1088,7 +1128,7 @@ static const struct { const char* name; const char* sig; } g_call_table[] = {
     {"zkmi_poly_lincomb_dev", "i d i b*4:56 i B32"}, {"zkmi_poly_evaluate_multi_dev", "i b*4:8 b*4:8 b*4:32 i b*4:32"}, {"zkmi_poly_div_by_zerofier_enqueue", "i d i i b32"},
     {"zkmi_plonk_split_t_dev", "i d i i b32 b32 d d d"},
     /* the host side of a Groth16 phase-2 contribution (js/groth16_phase2_native.js); point buffers are 2 * group * n8q bytes, checked here for BN254's size */
-    {"zkmi_phase2_key_from_seed", "i b32 b32 b64 b64"}, {"zkmi_phase2_hash_to_g2", "i b64 b128"}, {"zkmi_point_mul", "i i b64 b32 b64"},
+    {"zkmi_phase2_key_from_seed", "i b32 b32 b64 b64"}, {"zkmi_ptau_key_from_seed", "i b32 b96 b192 b192"}, {"zkmi_phase2_hash_to_g2", "i b64 b128"}, {"zkmi_point_mul", "i i b64 b32 b64"},
     /* the reference's generator by position (csrc/chacha.cuh): seed, first word | curve, seed; device output */
     {"zkmi_chacha_words_dev", "b32 i d i"}, {"zkmi_chacha_fr_dev", "i b32 d i B8"},
     /* the sequential generator on the host (include/zkmi_diag.h): what tests put in the kernels' place */
@@ -1342,7 +1382,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
         {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
-        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call},
+        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},
         {"devAlloc", js_dev_alloc}, {"devFree", js_dev_free}, {"memcpyH2D", js_memcpy_h2d}, {"memcpyD2H", js_memcpy_d2h},
