@@ -598,6 +598,18 @@ int zkmi_blake2b512_resume(const uint8_t* partial216, const uint8_t* data, size_
  * prv_keys, 3 x 32 bytes), then per key g1_s = G1.fromRng(rng) and g1_sx = prvKey * g1_s (3 x 2 n8q bytes each, affine Montgomery). Host only. */
 int zkmi_ptau_key_from_seed(int curve, const uint32_t seed8[8], uint8_t* prv_keys, uint8_t* g1_s, uint8_t* g1_sx);
 
+/* ---- the Lagrange sections of a prepared powers-of-tau file (src/powersoftau_preparephase2.js, src/powersoftau_convert.js) -----------
+ * zkmi_ptau_lagrange_section: for p = first .. top, G.ifft of the first 2^p points of `tau` (affine LEM points of `group`: section 2, 3, 4 or 5), the
+ * blocks back to back in the caller's pages: 2^(top + 1) - 2^first points, what the reference writes into section 12, 13, 14 or 15 power by power. With
+ * zero_last (tauG1: top = power + 1) the last point of the top block is taken as infinity and never read, and the section holds 2^top - 1 points.
+ * n_tau must equal 2^top - (zero_last ? 1 : 0); first <= top; first = top is the single transform powersOfTau.convert appends. All blocks are transformed
+ * in one pass of top + 2 launches over one work array (csrc/ptau_lagrange.cuh). top > Fr.s and top > 28 are refused with ZKMI_ERR_UNSUPPORTED before
+ * anything is allocated; refused while a pipeline slot holds work in flight. _dev: d_tau and d_out are device pointers of n_tau and
+ * 2^(top + 1) - 2^first points; the result is complete once the library stream has drained (any later library call that reads d_out is ordered behind it). */
+int zkmi_ptau_lagrange_section(int curve, int group, zkmi_pages tau, size_t n_tau, uint32_t first, uint32_t top, int zero_last, uint8_t* const* out_ptr,
+                               const size_t* out_len, int n_out_pages);
+int zkmi_ptau_lagrange_dev(int curve, int group, const void* d_tau, size_t n_tau, void* d_out, uint32_t first, uint32_t top, int zero_last);
+
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,
  * src/powersoftau_verify.js:358, src/mpc_applykey.js:64-70, src/zkey_export_bellman.js:36-83, src/zkey_new.js:103-115,373).

@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPtauPrepare) uninstallPtauPrepare(curve);          // unregister(snarkjs): preparePhase2 / convert of registerAll(snarkjs, { ptauPrepare: true })
     if (curve && curve.__zkmiPtauVerify) uninstallPtauVerify(curve);            // unregister(snarkjs): powersOfTau.verify of registerAll(snarkjs, { ptauVerify: true })
     if (curve && curve.__zkmiPhase2Verify) uninstallPhase2Verify(curve);    // unregister(snarkjs): verifyFromInit / verifyFromR1cs of registerAll(snarkjs, { phase2Verify: true })
     if (curve && curve.__zkmiPhase2) uninstallPhase2(curve);            // unregister(snarkjs): contribute / beacon of registerAll(snarkjs, { phase2: true }), before the setup gives the namespace back
@@ -214,6 +215,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.phase2) out.phase2 = installPhase2(snarkjs, options);
     if (options && options.phase2Verify) out.phase2Verify = installPhase2Verify(snarkjs, options);
     if (options && options.ptauVerify) out.ptauVerify = installPtauVerify(snarkjs, options);
+    if (options && options.ptauPrepare) out.ptauPrepare = installPtauPrepare(snarkjs, options);
     return out;
 }
 
@@ -382,6 +384,39 @@ function uninstallPtauVerify(snarkjs) {
     delete snarkjs.__zkmiPtauVerify;
 }
 
+// ---- powersOfTau.preparePhase2 / convert on the device (opt-in: registerAll(snarkjs, { ptauPrepare: true })) ----------------------------------------------
+// Through the patched curve methods preparePhase2 reaches the device once per power and section: G.lagrangeEvaluations -> G.ifft with an upload, p + 2 launches
+// and a download each, and a re-read of the source section in between. Here a section is one call that transforms all its powers in one pass
+// (js/powersoftau_prepare_native.js). Same arguments and the same bytes in the new file; both return undefined like the reference. Handed to the saved reference
+// function: any file that is not well-formed, power + 1 > Fr.s, a section beyond one 2^30-byte buffer, inputs the readers do not take.
+function installPtauPrepare(snarkjs, options) {
+    if (snarkjs.__zkmiPtauPrepare) return snarkjs.__zkmiPtauPrepare;
+    const prepareN = require("./powersoftau_prepare_native.js");
+    const saved = { preparePhase2: snarkjs.powersOfTau.preparePhase2, convert: snarkjs.powersOfTau.convert };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const run = (which) => async function (oldPtauFilename, newPTauFilename, logger) {
+        let raw;
+        try { raw = await prepareN[which](oldPtauFilename, { addon }); } catch (e) {
+            if (e instanceof prepareN.PrepareRefusal && e.handOver) return saved[which](oldPtauFilename, newPTauFilename, logger);
+            throw e;
+        }
+        if (typeof newPTauFilename === "string") require("fs").writeFileSync(newPTauFilename, raw);
+        else if (newPTauFilename && newPTauFilename.type === "file") require("fs").writeFileSync(newPTauFilename.fileName, raw);
+        else if (newPTauFilename && newPTauFilename.type === "mem") newPTauFilename.data = raw;
+        else throw new Error("powersOfTau." + which + ": expected a path or a fastfile descriptor for the new file");
+    };
+    // the namespace object in place now may already be the verifier's copy (installPtauVerify): keep whatever it holds, replace these two alone
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, { preparePhase2: run("preparePhase2"), convert: run("convert") }));
+    snarkjs.__zkmiPtauPrepare = { saved };
+    return snarkjs.__zkmiPtauPrepare;
+}
+function uninstallPtauPrepare(snarkjs) {
+    if (!snarkjs.__zkmiPtauPrepare) return;
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, snarkjs.__zkmiPtauPrepare.saved));
+    delete snarkjs.__zkmiPtauPrepare;
+}
+
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
 // plonk.setup reaches the device through the patched curve methods alone for its transforms and multiexps; the gate lowering, the permutation, the Lagrange
 // section and the selector buffers stay single-threaded JavaScript (src/plonk_setup.js). Replaced through the writable PROPERTY snarkjs.plonk: same
@@ -524,4 +559,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, loadAddon };

@@ -422,6 +422,25 @@ static napi_value js_ptau_section_check(napi_env env, napi_callback_info info) {
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
+/* ---- the Lagrange sections of a prepared powers-of-tau file (js/powersoftau_prepare_native.js)
+ * ptauLagrangeSection(curve, group, tau, nTau, first, top, zeroLast) -> Uint8Array: the blocks first .. top back to back, 2^(top + 1) - 2^first points */
+static napi_value js_ptau_lagrange_section(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    int32_t curve, group, zero_last; double n, first, top;
+    pages_t tau;
+    if (get_i32(env, argv[0], &curve) || get_i32(env, argv[1], &group) || (group != 1 && group != 2) || get_pages(env, argv[2], &tau) || get_f64(env, argv[3], &n) || n < 0 ||
+        n > 2147483647.0 || get_f64(env, argv[4], &first) || first < 0 || get_f64(env, argv[5], &top) || top < first || top > 28 || get_i32(env, argv[6], &zero_last) ||
+        !n8q_of_curve(curve)) BAD_ARG();
+    const size_t sg = 2 * (size_t)group * (size_t)n8q_of_curve(curve), ob = (((size_t)2 << (unsigned)top) - ((size_t)1 << (unsigned)first)) * sg;
+    uint8_t* out;
+    napi_value res = new_u8(env, ob, &out);
+    if (!res) BAD_ARG();
+    uint8_t* op[1] = {out};
+    const size_t ol[1] = {ob};
+    int rc = ZK_CALL(zkmi_ptau_lagrange_section(curve, group, as_zk(&tau), (size_t)n, (uint32_t)first, (uint32_t)top, zero_last, op, ol, 1));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* blake2bResume(partial216, data) -> Uint8Array(64): misc.fromPartialHash(partial).update(data).digest() */
 static napi_value js_blake2b_resume(napi_env env, napi_callback_info info) {
     ARGS(2);
@@ -1382,7 +1401,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
         {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
-        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume},
+        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},
         {"devAlloc", js_dev_alloc}, {"devFree", js_dev_free}, {"memcpyH2D", js_memcpy_h2d}, {"memcpyD2H", js_memcpy_d2h},

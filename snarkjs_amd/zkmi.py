@@ -46,7 +46,7 @@ SYMBOLS = [
     "zkmi_group_scale", "zkmi_group_scale_dev", "zkmi_group_scale_recode", "zkmi_phase2_key_from_seed", "zkmi_phase2_hash_to_g2", "zkmi_point_mul",
     "zkmi_chacha_words_dev", "zkmi_chacha_fr_dev", "zkmi_same_ratio_batch", "zkmi_phase2_section_ratio", "zkmi_phase2_h_ratio",
     "zkmi_chacha_block_host", "zkmi_chacha_struct_words_host", "zkmi_chacha_fr_host", "zkmi_chacha_fr_compact_host", "zkmi_chacha_set_round_blocks",
-    "zkmi_ptau_section_check", "zkmi_blake2b512_resume", "zkmi_ptau_key_from_seed",
+    "zkmi_ptau_section_check", "zkmi_blake2b512_resume", "zkmi_ptau_key_from_seed", "zkmi_ptau_lagrange_section", "zkmi_ptau_lagrange_dev",
 ]
 
 
@@ -327,6 +327,8 @@ def lib():
     L.zkmi_ptau_section_check.argtypes = [C.c_int, C.c_int, Pages, sz, C.POINTER(Pages), C.c_uint32, C.c_int, seed, seed, C.POINTER(vp), C.POINTER(sz), C.c_int, u8p, u8p, u8p]
     L.zkmi_blake2b512_resume.argtypes = [u8p, u8p, sz, u8p]
     L.zkmi_ptau_key_from_seed.argtypes = [C.c_int, seed, u8p, u8p, u8p]
+    L.zkmi_ptau_lagrange_section.argtypes = [C.c_int, C.c_int, Pages, sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_int]
+    L.zkmi_ptau_lagrange_dev.argtypes = [C.c_int, C.c_int, vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int]
     _lib = _Locked(L)
     return _lib
 
