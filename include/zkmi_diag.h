@@ -63,6 +63,32 @@ int zkmi_msm_sort_probe_dev(const void* d_scalars, size_t n, size_t scalar_bytes
                             uint32_t* counts, uint32_t* starts, size_t counts_cap, uint32_t* sorted, size_t sorted_cap, uint32_t* lane_g, uint32_t* lane_sub,
                             size_t lanes_cap, uint32_t* giants, size_t giants_cap, uint32_t* meta, zkmi_msm_sort_info* info);
 
+/* The back half of an MSM looked at from outside, for tests: runs ONE whole MSM through the product's own entry point and stages (msm_sort, then
+ * csrc/msm_host.hpp: msm_accumulate with its k_msm_tree / k_msm_giant launches, msm_reduce, msm_fold), waits for it, and copies out what the stages left.
+ *   table_handle  != 0: the MSM of zkmi_msm_table_dev over that table and the first n scalars (curve, group and d_bases are not read)
+ *                 0: the MSM of zkmi_msm_dev over n caller-owned device bases, with its R'-form copy and the width of zkmi_msm_set_window_bits
+ *   buckets       info->W * info->nb points, buckets_cap points of room: the finished buckets, g = window * nb + magnitude - 1 (window = 0 with a table);
+ *                 a bucket without list entries is reported as the point at infinity (the reduction never reads its stale words)
+ *   rowcol        2 * info->W << info->cbits points, rowcol_cap of room: the row and column sums in the order of msm_reduce's array,
+ *                 ((window * 2 + kind) << cbits) + i with kind 0 = row i (infinity for i >= 2^rbits), 1 = column i; bucket = row << cbits | column
+ *   result        the folded Jacobian point, as the entry point returns it (3 * group * n8q bytes)
+ * Points leave in the format of the bases: affine, Montgomery form, all-zero for the point at infinity, whichever form the device kept them in.
+ * Every output may be NULL (not copied); an array that is given and too small fails with ZKMI_ERR_INVALID after *info has been written — call once
+ * with NULL arrays to learn the sizes. *info is written once the MSM has run. Same entry rules as the two entry points; in particular the call is
+ * refused while the active pipeline slot holds work in flight. Product calls get no launch, copy or synchronisation for it: the picks are noted in host fields of the job. */
+typedef struct zkmi_msm_stage_info {
+    uint32_t c, W, nb;                   /* window bits; sets of buckets; buckets per set = 2^(c-1) */
+    uint32_t rbits, cbits;               /* the bucket grid: 2^rbits rows of 2^cbits columns */
+    uint32_t accum_kernel;               /* csrc/msm_select.hpp: MsmAccumKernel, 0 = accum29 ... 9 = accum32_wide */
+    uint32_t rowcol_kernel;              /* csrc/msm_select.hpp: MsmRowcolKernel, 0 wave29, 1 wave29_compact, 2 wave29_g2, 3 wave, 4 staged */
+    uint32_t r29_buckets;                /* 1: the finished buckets hold R'-form words */
+    uint32_t bitsums;                    /* 1: the weighted sums ran as plain bit sums (k_msm_bitsums / _lds) and a Horner on the host, 0: k_msm_wsum */
+    uint32_t cap;                        /* list entries per lane the schedule aimed at */
+    uint32_t lanes, multi_lanes, giants; /* lanes in all, lanes of multi-lane buckets (k_msm_tree's input), buckets of more than 128 lanes (k_msm_giant's) */
+} zkmi_msm_stage_info;
+int zkmi_msm_stage_probe_dev(uint64_t table_handle, int curve, int group, const void* d_bases, const void* d_scalars, size_t n, size_t scalar_bytes, uint8_t* buckets,
+                             size_t buckets_cap, uint8_t* rowcol, size_t rowcol_cap, uint8_t* result, zkmi_msm_stage_info* info);
+
 /* Device time (ms, HIP events) of the stages of the last proof, in order: buildABC, 6 NTTs, joinABC, sort(witness),
  * bucket accumulation of MSM B2, B1 (+ the second witness sort), A, C, sort(H scalars), accumulation of MSM H, batched G1 bucket reductions (the B2
  * reduction runs on a second stream underneath the G1 accumulations).

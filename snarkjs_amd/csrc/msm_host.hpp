@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <vector>
 #include "host_field.hpp"
 #include "msm.cuh"
 #include "msm29.cuh"
@@ -126,6 +127,10 @@ struct MsmJob {
     uint32_t* h_win = nullptr;                      // pinned host: 2W weighted sums then 2W totals (XYZZ)
     const uint32_t *buckets = nullptr, *counts = nullptr;   // device: this job's complete buckets (between accumulate and reduce)
     hipEvent_t acc0 = nullptr, acc1 = nullptr;      // bracket the k_msm_accum launch (bench.py roofline: live kernel time)
+    // which kernels the picks chose and where msm_reduce left this job's row / column sums (host bookkeeping for zkmi_msm_stage_probe_dev, as
+    // MsmPlan::Path is for the sort probe; nothing on the device reads it): MsmAccumKernel / MsmRowcolKernel as integers, -1 before the stage has run
+    int accum_kernel = -1, rowcol_kernel = -1;
+    const uint32_t* rowcol = nullptr;               // device: 2 W 2^cbits XYZZ points, ((w * 2 + kind) << cbits) + i; valid until the next msm_reduce on the stream
 };
 constexpr int MSM_JOB_SLOTS = 8;
 constexpr size_t MSM_JOB_SLOT_BYTES = 512 * 1024;
@@ -240,6 +245,7 @@ template <class F> int msm_accumulate(const void* d_bases, const MsmPlan& pl, ui
     job.W = sh.W; job.c = sh.c; job.nb = sh.nb; job.buckets = buckets; job.counts = pl.counts;
     job.merged = into != nullptr;
     job.r29 = pick.r29_buckets;
+    job.accum_kernel = (int)pick.kernel;
     if (into) {
         uint32_t* cmb;
         ZK_TRY(ws_get("msm.cmbcounts." + std::to_string(into->slot), total * 4, (void**)&cmb));
@@ -382,6 +388,8 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
         MsmJob& job = *jobs[i];
         job.cbits = (int)cbits;
         job.bitsums = bitsums ? 1 : 0;
+        job.rowcol_kernel = (int)rp.kernel;
+        job.rowcol = rc + (size_t)i * 2 * W * C * PW;
         if (perA * 4 * 2 > MSM_JOB_SLOT_BYTES) return fail(ZKMI_ERR_UNSUPPORTED, "msm: too many windows");
         ZK_HIP(hipMemcpyAsync(job.h_win, resA + (size_t)i * perA, perA * 4, hipMemcpyDeviceToHost, st));
         if (!bitsums) ZK_HIP(hipMemcpyAsync(job.h_win + perA, resR + (size_t)i * perA, perA * 4, hipMemcpyDeviceToHost, st));
@@ -415,6 +423,72 @@ template <class F> void msm_fold(const MsmJob& job, uint8_t* out_jac) {
     msm_fold_windows<F>(win.data(), tot.data(), job.W, job.c, job.cbits, out_jac);
 }
 
+// ---- zkmi_msm_stage_probe_dev (include/zkmi_diag.h): the back half of ONE MSM looked at from outside ------------------------------------------
+// While a sink is set (by the probe alone, for the length of its call), msm_run and msm_run_table hand over what the job they have just finished
+// left on the device: finished buckets and row / column sums as affine points. A product call finds the pointer null and does nothing more.
+struct MsmStageSink {
+    uint8_t *buckets = nullptr, *rowcol = nullptr;  // host arrays of the caller (may be null), with room for this many points
+    size_t buckets_cap = 0, rowcol_cap = 0;
+    zkmi_msm_stage_info info = {};
+    bool ran = false;                               // info has been written
+};
+MsmStageSink*& msm_stage_sink();                    // msm_sort.hip
+
+// n XYZZ points (device words as the kernels store them, R-form or R'-form: x = X / ZZ and y = Y / ZZZ do not see a common factor of the four
+// coordinates) -> affine points in the reference's R-form, all-zero for the point at infinity; live (optional): a zero word marks a point that
+// was never written. One inversion in all (Montgomery's trick).
+template <class F> void xyzz_words_to_affine(const uint32_t* src, const uint32_t* live, size_t n, uint8_t* dst) {
+    typedef typename HostOf<F>::FT FT;
+    typedef typename FT::E E;
+    constexpr int FW = FieldWords<F>::value, PW = 4 * FW;
+    const FT Fh = HostOf<F>::make();
+    auto coord = [&](size_t i, int k) { E v; memcpy(&v, src + i * PW + (size_t)k * FW, 4 * FW); return v; };
+    std::vector<E> pre(n);                          // pre[i] = product of ZZ ZZZ over the finite points before i
+    std::vector<uint8_t> fin(n);
+    E run = Fh.One();
+    for (size_t i = 0; i < n; i++) {
+        pre[i] = run;
+        fin[i] = (!live || live[i]) && !coord(i, 2).is_zero();
+        if (fin[i]) run = Fh.mul(run, Fh.mul(coord(i, 2), coord(i, 3)));
+    }
+    E inv = Fh.inv(run);
+    for (size_t i = n; i-- > 0;) {
+        uint8_t* o = dst + i * 2 * 4 * FW;
+        if (!fin[i]) { memset(o, 0, 2 * 4 * FW); continue; }
+        const E zz = coord(i, 2), zzz = coord(i, 3), both = Fh.mul(inv, pre[i]);      // 1 / (ZZ ZZZ) of this point
+        inv = Fh.mul(inv, Fh.mul(zz, zzz));
+        const E x = Fh.mul(coord(i, 0), Fh.mul(both, zzz)), y = Fh.mul(coord(i, 1), Fh.mul(both, zz));
+        memcpy(o, &x, 4 * FW); memcpy(o + 4 * FW, &y, 4 * FW);
+    }
+}
+// after the stream has been synchronised and the job folded
+template <class F> int msm_stage_collect(MsmStageSink& sk, const MsmPlan& pl, const MsmJob& job) {
+    constexpr int PW = 4 * FieldWords<F>::value;
+    uint32_t m[3] = {0, 0, 0};
+    ZK_HIP(hipMemcpy(m, pl.meta, sizeof m, hipMemcpyDeviceToHost));
+    zkmi_msm_stage_info& r = sk.info;
+    r.c = (uint32_t)job.c; r.W = (uint32_t)job.W; r.nb = job.nb; r.cbits = (uint32_t)job.cbits; r.rbits = (uint32_t)(job.c - 1 - job.cbits);
+    r.accum_kernel = (uint32_t)job.accum_kernel; r.rowcol_kernel = (uint32_t)job.rowcol_kernel;
+    r.r29_buckets = job.r29; r.bitsums = (uint32_t)job.bitsums;
+    r.cap = pl.cap; r.lanes = m[0]; r.multi_lanes = m[1]; r.giants = m[2];
+    sk.ran = true;
+    const size_t total = (size_t)job.W * job.nb, n_rc = ((size_t)2 * job.W) << job.cbits;
+    if (total != pl.total || !job.buckets || !job.counts || !job.rowcol) return fail(ZKMI_ERR_INVALID, "msm_stage_probe: the job did not pass through every stage");
+    if ((sk.buckets && sk.buckets_cap < total) || (sk.rowcol && sk.rowcol_cap < n_rc)) return fail(ZKMI_ERR_INVALID, "msm_stage_probe: an output array is too small (sizes are in *info)");
+    if (sk.buckets) {
+        std::vector<uint32_t> w(total * PW), live(total);
+        ZK_HIP(hipMemcpy(live.data(), job.counts, total * 4, hipMemcpyDeviceToHost));
+        ZK_HIP(hipMemcpy(w.data(), job.buckets, total * PW * 4, hipMemcpyDeviceToHost));
+        xyzz_words_to_affine<F>(w.data(), live.data(), total, sk.buckets);
+    }
+    if (sk.rowcol) {
+        std::vector<uint32_t> w(n_rc * PW);
+        ZK_HIP(hipMemcpy(w.data(), job.rowcol, n_rc * PW * 4, hipMemcpyDeviceToHost));
+        xyzz_words_to_affine<F>(w.data(), nullptr, n_rc, sk.rowcol);
+    }
+    return ZKMI_OK;
+}
+
 // Full device MSM: bases (affine, device), scalars (plain integers, device) -> Jacobian point on the host.
 template <class F> int msm_run(const void* d_bases, const void* d_scalars, size_t n, size_t sb, uint8_t* out_jac) {
     constexpr int FW = FieldWords<F>::value;
@@ -435,6 +509,7 @@ template <class F> int msm_run(const void* d_bases, const void* d_scalars, size_
     float ms = 0;
     if (hipEventElapsedTime(&ms, cx.ev0, cx.ev1) == hipSuccess) cx.last_ms = ms;
     msm_fold<F>(job, out_jac);
+    if (MsmStageSink* sk = msm_stage_sink()) return msm_stage_collect<F>(*sk, pl, job);
     return ZKMI_OK;
 }
 
@@ -498,6 +573,7 @@ template <class F> int msm_run_table(const void* d_table, size_t stride, int c, 
     float ms = 0;
     if (hipEventElapsedTime(&ms, cx.ev0, cx.ev1) == hipSuccess) cx.last_ms = ms;
     msm_fold<F>(job, out_jac);
+    if (MsmStageSink* sk = msm_stage_sink()) return msm_stage_collect<F>(*sk, pl, job);
     return ZKMI_OK;
 }
 

@@ -190,6 +190,10 @@ int msm_sort(const void* d_scalars, size_t n, size_t sb, MsmPlan& pl, int plan_s
     return ZKMI_OK;
 }
 
+MsmStageSink*& msm_stage_sink() {
+    static MsmStageSink* sink = nullptr;
+    return sink;
+}
 MsmMultiPending& msm_multi_pending(int pipe) {
     static MsmMultiPending pend[2];
     return pend[pipe & 1];

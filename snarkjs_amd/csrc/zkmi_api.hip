@@ -611,6 +611,29 @@ int zkmi_msm_sort_probe_dev(const void* d_scalars, size_t n, size_t scalar_bytes
     if (meta) memcpy(meta, m, sizeof m);
     return ZKMI_OK;
 }
+// One whole MSM through zkmi_msm_table_dev / zkmi_msm_dev with a sink set (include/zkmi_diag.h; csrc/msm_host.hpp: msm_stage_collect): the entry points
+// themselves run, so the probe sees the stages exactly as a product call drives them.
+int zkmi_msm_stage_probe_dev(uint64_t table_handle, int curve, int group, const void* d_bases, const void* d_scalars, size_t n, size_t scalar_bytes, uint8_t* buckets,
+                             size_t buckets_cap, uint8_t* rowcol, size_t rowcol_cap, uint8_t* result, zkmi_msm_stage_info* info) {
+    ZK_TRY(require_ctx());
+    if (!d_scalars || !info || !n) return fail(ZKMI_ERR_INVALID, "msm_stage_probe: null argument or no terms");
+    if (!table_handle && !d_bases) return fail(ZKMI_ERR_INVALID, "msm_stage_probe: neither a table nor bases");
+    ZK_TRY(slot_idle_or_fail("msm_stage_probe"));
+    uint8_t jac[3 * 2 * 48];
+    MsmStageSink sk;
+    sk.buckets = buckets; sk.buckets_cap = buckets_cap; sk.rowcol = rowcol; sk.rowcol_cap = rowcol_cap;
+    msm_stage_sink() = &sk;
+    const int rc = table_handle ? zkmi_msm_table_dev(table_handle, d_scalars, n, scalar_bytes, jac) : zkmi_msm_dev(curve, group, d_bases, d_scalars, n, scalar_bytes, jac);
+    msm_stage_sink() = nullptr;
+    if (sk.ran) *info = sk.info;
+    if (rc) return rc;
+    if (!sk.ran) return fail(ZKMI_ERR_INVALID, "msm_stage_probe: the MSM did not run its stages");
+    if (result) {
+        if (table_handle) { const MsmTable& t = g_tables.find(table_handle)->second; curve = t.curve; group = t.group; }
+        memcpy(result, jac, (size_t)3 * group * n8q_of(curve));
+    }
+    return ZKMI_OK;
+}
 // ---- content-addressed cache of resident base tables behind zkmi_msm ---------------------------------------------------------
 // zkey sections and SRS slices are static, so the same bytes come back on every proof; their pre-computed window tables stay on
 // the device. The cache is keyed by the CONTENT of the base buffer — a 128-bit hash of every 64 KiB chunk, computed by the

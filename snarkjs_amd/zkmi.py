@@ -23,7 +23,7 @@ SYMBOLS = [
     "zkmi_groth16_load_paged", "zkmi_groth16_load_shard_paged", "zkmi_groth16_prove_paged", "zkmi_groth16_build_abc_dev", "zkmi_groth16_coef_layout", "zkmi_msm_dev_fallbacks",
     "zkmi_init", "zkmi_device_count", "zkmi_last_error", "zkmi_version", "zkmi_set_stream", "zkmi_synchronize",
     "zkmi_dev_alloc", "zkmi_dev_free", "zkmi_memcpy_h2d", "zkmi_memcpy_d2h", "zkmi_memcpy_d2d", "zkmi_memset_dev",
-    "zkmi_msm", "zkmi_release_bases", "zkmi_msm_dev", "zkmi_msm_sort_probe_dev", "zkmi_msm_set_window_bits", "zkmi_msm_accum_ms", "zkmi_msm_stats", "zkmi_msm_accum_additions", "zkmi_msm_table_build", "zkmi_msm_table_dev", "zkmi_msm_table_multi_dev", "zkmi_msm_table_multi_enqueue_dev", "zkmi_msm_table_multi_collect", "zkmi_msm_table_release", "zkmi_msm_table_info",
+    "zkmi_msm", "zkmi_release_bases", "zkmi_msm_dev", "zkmi_msm_sort_probe_dev", "zkmi_msm_stage_probe_dev", "zkmi_msm_set_window_bits", "zkmi_msm_accum_ms", "zkmi_msm_stats", "zkmi_msm_accum_additions", "zkmi_msm_table_build", "zkmi_msm_table_dev", "zkmi_msm_table_multi_dev", "zkmi_msm_table_multi_enqueue_dev", "zkmi_msm_table_multi_collect", "zkmi_msm_table_release", "zkmi_msm_table_info",
     "zkmi_ipc_export", "zkmi_ipc_open", "zkmi_ipc_close", "zkmi_peer_copy", "zkmi_peer_copy_async", "zkmi_peer_fence", "zkmi_groth16_key_curve", "zkmi_groth16_reset",
     "zkmi_ntt", "zkmi_ntt_dev",
     "zkmi_fr_batch_apply_key", "zkmi_fr_batch_apply_key_dev", "zkmi_fr_batch", "zkmi_fr_batch_dev",
@@ -129,6 +129,11 @@ class MsmSortInfo(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("c", "Wd", "W", "nb", "total", "cap", "nw", "radix", "lb", "parts", "fused_cap", "staged", "chunks", "entries", "lanes", "giants")]
 
 
+class MsmStageInfo(C.Structure):
+    """zkmi_msm_stage_info (include/zkmi_diag.h): the shape of the bucket grid of zkmi_msm_stage_probe_dev and the kernels its stages picked"""
+    _fields_ = [(k, C.c_uint32) for k in ("c", "W", "nb", "rbits", "cbits", "accum_kernel", "rowcol_kernel", "r29_buckets", "bitsums", "cap", "lanes", "multi_lanes", "giants")]
+
+
 class _Locked:
     """The library behind one process-wide re-entrant lock: include/zkmi.h declares it single-caller per process (process-global pipeline
     slot, streams and scratch), and ctypes drops the GIL for the duration of a call. Attribute access hands out a locking wrapper of the
@@ -187,6 +192,7 @@ def lib():
     L.zkmi_msm_dev.argtypes = [C.c_int, C.c_int, vp, vp, sz, sz, u8p]
     L.zkmi_msm_set_window_bits.argtypes = [C.c_int]
     L.zkmi_msm_sort_probe_dev.argtypes = [vp, sz, sz, C.c_int, sz, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, C.POINTER(MsmSortInfo)]
+    L.zkmi_msm_stage_probe_dev.argtypes = [C.c_uint64, C.c_int, C.c_int, vp, vp, sz, sz, vp, sz, vp, sz, u8p, C.POINTER(MsmStageInfo)]
     L.zkmi_msm_table_build.argtypes = [C.c_int, C.c_int, vp, sz, C.POINTER(C.c_uint64)]
     L.zkmi_msm_table_dev.argtypes = [C.c_uint64, vp, sz, sz, u8p]
     L.zkmi_msm_table_multi_dev.argtypes = [C.c_uint64, C.POINTER(vp), C.POINTER(sz), C.c_int, sz, u8p]
