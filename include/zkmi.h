@@ -610,6 +610,23 @@ int zkmi_ptau_lagrange_section(int curve, int group, zkmi_pages tau, size_t n_ta
                                const size_t* out_len, int n_out_pages);
 int zkmi_ptau_lagrange_dev(int curve, int group, const void* d_tau, size_t n_tau, void* d_out, uint32_t first, uint32_t top, int zero_last);
 
+/* ---- a phase-1 contribution (src/powersoftau_contribute.js, src/powersoftau_beacon.js) -------------------------------------------------
+ * zkmi_ptau_contribute_section: everything a contribution needs of one section (2, 3, 4 or 5), from one upload. `in` holds n affine LEM points of `group`;
+ * first / inc are Montgomery Fr elements (host pointers).
+ *   lem   out_i = (first * inc^i) * P_i, what G.batchApplyKey(buff, first, inc) returns chunk after chunk: the bytes of the new file
+ *   c     the same points in C form (G.batchLEMtoC: half the size), the bytes the response hash takes
+ *   u     the same points in U form (G.batchLEMtoU), the bytes the next challenge hash takes
+ * Each output is a list of pages whose lengths add up to exactly n points. group == 1 runs the per-lane-scalar kernel of csrc/ptau_contribute.cuh in slices
+ * of at most 2^20 points (slice s starts from first * inc^(s * slice)), group == 2 the general kernel of zkmi_group_batch_apply_key_dev; both conversions run
+ * on the resident LEM result. n == 0 returns ZKMI_OK and touches nothing. ZKMI_ERR_INVALID for an unknown curve or group, a null pointer, page totals that do
+ * not match n, and while a pipeline slot holds work in flight (the slot keeps its work).
+ * zkmi_blake2b512_partial: misc.toPartialHash (src/misc.js:111-127) of a fresh Blake2b-512 hasher after one `update` per chunk, the 216 bytes
+ * zkmi_blake2b512_resume takes. The first 128 bytes are the reference's block buffer as those update calls leave it: a full block that more bytes of the
+ * same call follow is hashed straight from the input and never copied, so the bytes beyond the position depend on how the data was cut into calls. Host only. */
+int zkmi_ptau_contribute_section(int curve, int group, zkmi_pages in, size_t n, const uint8_t* first, const uint8_t* inc, uint8_t* const* lem_ptr, const size_t* lem_len,
+                                 int n_lem_pages, uint8_t* const* c_ptr, const size_t* c_len, int n_c_pages, uint8_t* const* u_ptr, const size_t* u_len, int n_u_pages);
+int zkmi_blake2b512_partial(const uint8_t* const* chunks, const size_t* lens, int n, uint8_t* partial216);
+
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,
  * src/powersoftau_verify.js:358, src/mpc_applykey.js:64-70, src/zkey_export_bellman.js:36-83, src/zkey_new.js:103-115,373).

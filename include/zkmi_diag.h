@@ -185,6 +185,14 @@ int zkmi_chacha_struct_words_host(const uint32_t seed8[8], uint64_t first_word, 
 int zkmi_chacha_fr_host(int curve, const uint32_t seed8[8], uint8_t* out, size_t n, uint64_t* words_consumed);
 int zkmi_chacha_fr_compact_host(int curve, const uint32_t seed8[8], uint8_t* out, size_t n, uint64_t* words_consumed);
 int zkmi_chacha_set_round_blocks(size_t blocks);
+/* The G1 kernel of zkmi_ptau_contribute_section on its own (csrc/ptau_contribute.cuh): out_i = k_i * P_i for n affine LEM points and n scalars of 32 bytes,
+ * little-endian, normal form, below 2^255 (device pointers; d_out must not overlap d_points). group must be 1: group 2 returns ZKMI_ERR_UNSUPPORTED, it has no
+ * such kernel (the group argument is there for that refusal alone). Refused while a pipeline slot holds work in flight. Like every _dev entry the call only
+ * enqueues on the library stream and returns: d_out is complete once that stream has drained (zkmi_synchronize, or any later library call or zkmi_memcpy_d2h, which
+ * are ordered behind it). Scalars of r and above are taken as they are: the digits are read from the bits, so k P comes out for every k below 2^255.
+ * zkmi_diag_set_ptau_slice: points per slice of zkmi_ptau_contribute_section (0 restores the default of 2^20); the result does not depend on it. */
+int zkmi_diag_group_mul_each_dev(int curve, int group, const void* d_points, const void* d_scalars_normal, void* d_out, size_t n);
+int zkmi_diag_set_ptau_slice(size_t points);
 
 #ifdef __cplusplus
 }

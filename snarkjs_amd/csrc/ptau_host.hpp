@@ -78,6 +78,34 @@ struct Blake2b512 {
             pos += take; length += take; data += take; len -= take;
         }
     }
+    // One `update` call of the reference's hasher (the Blake2 base class of its bundle), which the block buffer remembers: a full block that more bytes
+    // of the SAME call follow is compressed straight from the input and never copied, so the bytes of the buffer beyond `pos` are whatever an earlier
+    // copy left there. update() above gives the same digest for any cut of the data but copies every block; misc.toPartialHash writes the whole buffer
+    // into the file, so a contribution's 216 bytes need this path. (The reference takes the direct path only for input whose byte offset in its
+    // ArrayBuffer is a multiple of 4; its callers pass whole buffers.)
+    void update_call(const uint8_t* data, size_t len) {
+        size_t c = 0;
+        while (c < len) {
+            if (pos == 128) { compress(buf, false); pos = 0; }
+            const size_t take = len - c < 128 - pos ? len - c : 128 - pos;
+            if (take != 128 || !(c + take < len)) {
+                memcpy(buf + pos, data + c, take);
+                pos += take; length += take; c += take;
+            } else {
+                for (; c + 128 < len; c += 128) { length += 128; compress(data + c, false); }
+            }
+        }
+    }
+    // misc.toPartialHash: the inverse of restore(); words 17 and 19 stay zero and word 16 is length - pos cut to 32 bits, as the reference writes them
+    void partial(uint8_t* partial216) const {
+        memcpy(partial216, buf, 128);
+        uint32_t w[22];
+        memset(w, 0, sizeof w);
+        for (int i = 0; i < 8; i++) { w[2 * i] = (uint32_t)h[i]; w[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+        w[16] = (uint32_t)(length - pos);
+        w[18] = (uint32_t)pos;
+        memcpy(partial216 + 128, w, 88);
+    }
     void digest(uint8_t* out64) {
         memset(buf + pos, 0, 128 - pos);
         compress(buf, true);

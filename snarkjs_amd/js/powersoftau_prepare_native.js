@@ -109,4 +109,4 @@ async function run(src, options, isConvert) {
 const preparePhase2 = (src, options) => run(src, options, false);
 const convert = (src, options) => run(src, options, true);
 
-module.exports = { preparePhase2, convert, deviceOf, PrepareRefusal };
+module.exports = { preparePhase2, convert, deviceOf, PrepareRefusal, open, headerOf, fileOf };

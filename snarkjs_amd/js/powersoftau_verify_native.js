@@ -256,4 +256,4 @@ async function verify(src, options) {
     } finally { rd.close(); }
 }
 
-module.exports = { verify, deviceOf, readContributions, firstChallengeHash, PtauRefusal };
+module.exports = { verify, deviceOf, readContributions, firstChallengeHash, g2sp, PtauRefusal };

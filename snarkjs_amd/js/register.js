@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPtauContribute) uninstallPtauContribute(curve);    // unregister(snarkjs): newAccumulator / contribute / beacon of registerAll(snarkjs, { ptauContribute: true })
     if (curve && curve.__zkmiPtauPrepare) uninstallPtauPrepare(curve);          // unregister(snarkjs): preparePhase2 / convert of registerAll(snarkjs, { ptauPrepare: true })
     if (curve && curve.__zkmiPtauVerify) uninstallPtauVerify(curve);            // unregister(snarkjs): powersOfTau.verify of registerAll(snarkjs, { ptauVerify: true })
     if (curve && curve.__zkmiPhase2Verify) uninstallPhase2Verify(curve);    // unregister(snarkjs): verifyFromInit / verifyFromR1cs of registerAll(snarkjs, { phase2Verify: true })
@@ -216,6 +217,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.phase2Verify) out.phase2Verify = installPhase2Verify(snarkjs, options);
     if (options && options.ptauVerify) out.ptauVerify = installPtauVerify(snarkjs, options);
     if (options && options.ptauPrepare) out.ptauPrepare = installPtauPrepare(snarkjs, options);
+    if (options && options.ptauContribute) out.ptauContribute = installPtauContribute(snarkjs, options);
     return out;
 }
 
@@ -417,6 +419,70 @@ function uninstallPtauPrepare(snarkjs) {
     delete snarkjs.__zkmiPtauPrepare;
 }
 
+// ---- powersOfTau.newAccumulator / contribute / beacon on the device (opt-in: registerAll(snarkjs, { ptauContribute: true })) --------------------------------
+// Through the patched curve methods a contribution feeds G.batchApplyKey and the two conversions 2^20 / sG points at a time, an upload, a launch of the general
+// kernel and a download each; here a section is one call (js/powersoftau_contribute_native.js). Same arguments, the same draw of 64 bytes
+// (globalThis.crypto.getRandomValues where the reference's browser build uses it), the same bytes in the new file, the same result: the response hash
+// (newAccumulator: the first challenge hash); beacon returns false with the reference's logger.error where it refuses. Handed to the saved reference function:
+// whatever the driver marks handOver (a file that is not well-formed, power 0, an empty entropy, a section beyond one buffer, ...).
+function installPtauContribute(snarkjs, options) {
+    if (snarkjs.__zkmiPtauContribute) return snarkjs.__zkmiPtauContribute;
+    const contribN = require("./powersoftau_contribute_native.js");
+    const saved = { newAccumulator: snarkjs.powersOfTau.newAccumulator, contribute: snarkjs.powersOfTau.contribute, beacon: snarkjs.powersOfTau.beacon };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const dev = options && options.dev;
+    const logOf = (logger) => (level, text) => { if (logger && typeof logger[level] === "function") logger[level](text); };
+    function store(target, raw, what) {
+        if (typeof target === "string") require("fs").writeFileSync(target, raw);
+        else if (target && target.type === "file") require("fs").writeFileSync(target.fileName, raw);
+        else if (target && target.type === "mem") target.data = raw;
+        else throw new Error(what + ": expected a path or a fastfile descriptor for the new file");
+    }
+    // run the driver; null: the call goes to the saved function
+    async function attempt(f, logger) {
+        try { return await f(); } catch (e) {
+            if (!(e instanceof contribN.ContributeRefusal)) throw e;
+            if (e.handOver) return null;
+            if (e.throws) throw new Error(e.message);
+            if (!e.logged && logger) logger.error(e.message);
+            return false;
+        }
+    }
+    async function newAccumulator(curve, power, fileName, logger) {
+        const res = await attempt(() => contribN.newAccumulator(curve, power, { log: logOf(logger) }), logger);
+        if (res === null) return saved.newAccumulator(curve, power, fileName, logger);
+        store(fileName, res.ptau, "powersOfTau.newAccumulator");
+        return res.firstChallengeHash;
+    }
+    async function contribute(oldPtauFilename, newPTauFilename, name, entropy, logger) {
+        if (!entropy) return saved.contribute(oldPtauFilename, newPTauFilename, name, entropy, logger);
+        const random64 = new Uint8Array(64);
+        if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random64); else require("crypto").randomFillSync(random64);
+        const res = await attempt(() => contribN.contribute(oldPtauFilename, name, entropy, { addon, dev, random64, log: logOf(logger) }), logger);
+        // the saved function draws its own 64 bytes: a pinned stream differs from the reference's by this one draw, on calls the reference fails or refuses anyway
+        if (res === null) return saved.contribute(oldPtauFilename, newPTauFilename, name, entropy, logger);
+        store(newPTauFilename, res.ptau, "powersOfTau.contribute");
+        return res.responseHash;
+    }
+    async function beacon(oldPtauFilename, newPTauFilename, name, beaconHashStr, numIterationsExp, logger) {
+        const res = await attempt(() => contribN.beacon(oldPtauFilename, name, beaconHashStr, numIterationsExp, { addon, dev, log: logOf(logger) }), logger);
+        if (res === null) return saved.beacon(oldPtauFilename, newPTauFilename, name, beaconHashStr, numIterationsExp, logger);
+        if (res === false) return false;
+        store(newPTauFilename, res.ptau, "powersOfTau.beacon");
+        return res.responseHash;
+    }
+    // the namespace object in place now may already be another installer's copy: keep whatever it holds, replace these three alone
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, { newAccumulator, contribute, beacon }));
+    snarkjs.__zkmiPtauContribute = { saved };
+    return snarkjs.__zkmiPtauContribute;
+}
+function uninstallPtauContribute(snarkjs) {
+    if (!snarkjs.__zkmiPtauContribute) return;
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, snarkjs.__zkmiPtauContribute.saved));
+    delete snarkjs.__zkmiPtauContribute;
+}
+
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
 // plonk.setup reaches the device through the patched curve methods alone for its transforms and multiexps; the gate lowering, the permutation, the Lagrange
 // section and the selector buffers stay single-threaded JavaScript (src/plonk_setup.js). Replaced through the writable PROPERTY snarkjs.plonk: same
@@ -559,4 +625,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, loadAddon };
