@@ -137,6 +137,7 @@ int zkmi_msm_table_info(uint64_t handle, int* curve, int* group, size_t* n);
  *   X[k] = sum_j x[j] w^(jk), w = Fr.w[log_n], natural order in and out; inverse includes the 1/n scaling.
  * n = 2^log_n elements of 32 bytes; log_n must be <= Fr.s (28 BN254, 32 BLS12-381) — the reference's extra
  * n = 2^(s+1) coset case (@216148) is rejected with ZKMI_ERR_UNSUPPORTED.
+ * Sizes above 2^24 run four passes over the array instead of at most three; they are tested at 2^25 / 2^26 (tests/test_gpu_ntt_passes.py).
  * Optional fused pre-scale x[i] <- x[i]*first*inc^i (= Fr.batchApplyKey in front, src/groth16_prove.js:66-76):
  * pass prescale_first = prescale_inc = NULL for a plain transform. */
 int zkmi_ntt(int curve, zkmi_pages in, uint8_t* const* out_ptr, const size_t* out_len, int n_out_pages, unsigned log_n,

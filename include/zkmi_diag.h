@@ -110,6 +110,14 @@ int zkmi_calibrate_code_fetch(double* small_loop_gmul_per_s, double* big_loop_gm
  * either way. -1: no device. */
 int zkmi_compact_code(void);
 
+/* How zkmi_ntt* would run a transform of 2^log_n points in THIS process: *n_pass = the passes over the array (1..4), l[0..4) = the digit widths of the
+ * passes, most significant input digit first (they sum to log_n; unused entries 0), *limbs29 = 1 when the passes run on 9 x 29-bit limbs (csrc/ntt29.cuh),
+ * 0 on saturated 32-bit limbs (csrc/ntt.cuh). The answer comes from the functions the driver itself decides with (csrc/ntt_plan.hpp) and follows the
+ * switches it reads once per process: ZKMI_NTT_DIGIT (bits per digit at most, default 8: one pass up to 2^9, two up to 2^16, three up to 2^24, four from
+ * 2^25 to Fr.s), ZKMI_NTT29 and ZKMI_NTT29_MAX_LOG. Fails as the transform would, with ZKMI_ERR_UNSUPPORTED: log_n above Fr.s, or a digit cap under which
+ * 2^log_n would need more than four passes (or a cap outside 1..9); the outputs are not written then. Host only, needs no device; any output may be NULL. */
+int zkmi_ntt_plan_probe(int curve, unsigned log_n, uint32_t* n_pass, uint32_t l[4], int* limbs29);
+
 /* Synthetic base table of SURVEY.md §8d: P_i = (f*g^i mod r)*G written to device memory as affine Montgomery points
  * (what G.batchApplyKey(G repeated n, Fr.e(f), Fr.e(g)) returns).  For benchmarks and tests. */
 int zkmi_gen_geometric_bases_dev(int curve, int group, size_t n, uint64_t f, uint64_t g, void* d_out);

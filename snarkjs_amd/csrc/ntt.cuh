@@ -17,17 +17,10 @@
 // per-pass row factors.
 #pragma once
 #include "field.cuh"
+#include "ntt_plan.hpp"                  // NTT_MAX_PASSES, NTT_TILE_LOG and the digit split
 
 namespace zkmi {
 
-constexpr int NTT_MAX_PASSES = 4;
-#ifndef ZKMI_NTT_TILE_LOG
-#define ZKMI_NTT_TILE_LOG 9
-#endif
-// 512 elements = 16 KiB of LDS per workgroup -> 8 workgroups (8 waves per SIMD) per CU: the butterflies are latency-bound carry
-// chains, occupancy matters more than tile size (2^20 transform: 0.150 ms; 1024-element tiles 0.163 ms; 2048-element tiles 0.180 ms;
-// A/B on one box, PLONK's 2^22 transforms unchanged)
-constexpr int NTT_TILE_LOG = ZKMI_NTT_TILE_LOG;
 constexpr int NTT_THREADS = 256;
 
 struct NttPassArgs {

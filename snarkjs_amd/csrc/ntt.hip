@@ -47,22 +47,26 @@ static int upload_table(const std::vector<HE>& t, uint32_t** d) {
     return ZKMI_OK;
 }
 
+// The plan of a transform of 2^L points: the digit split of ntt_plan.hpp (ntt_split) and the tables its passes read. With the default digit cap
+// of 8 bits a transform is ONE pass up to 2^9 (one tile), TWO up to 2^16, THREE up to 2^24 and FOUR from 2^25 to Fr.s (2^28 on BN254, 2^32 on
+// BLS12-381; 2^25 splits 7,6,6,6 and 2^26 7,7,6,6). Four passes (NTT_MAX_PASSES) is all that the plan, NttPassArgs and the pre-scale tables hold:
+// a ZKMI_NTT_DIGIT that would need more is refused here (ZKMI_ERR_UNSUPPORTED), before anything is allocated, uploaded or launched. The four-pass
+// sizes are held to closed forms at 2^25 / 2^26 and, with the cap lowered, to the oracle at 2^10..2^18 by tests/test_gpu_ntt_passes.py; the
+// split itself is pinned by tests/test_ntt_plan_host.py.
 template <class C> static int get_plan(int curve, unsigned L, int inverse, NttPlan** out) {
     Ctx& cx = ctx();
     auto key = std::make_tuple(curve, L, inverse);
     auto it = cx.plans.find(key);
     if (it != cx.plans.end()) { *out = &it->second; return ZKMI_OK; }
+    NttSplit split;
+    std::string why;
+    if (int rc = ntt_split_env(L, &split, &why)) return fail(rc, why);
     const FrRoots& R = fr_roots<C>();
     const HFr& F = R.F;
     NttPlan P;
     P.log_n = L;
-    if (L <= (unsigned)NTT_TILE_LOG) { P.n_pass = 1; P.l[0] = L; }
-    else {
-        static const unsigned maxbits = getenv("ZKMI_NTT_DIGIT") ? (unsigned)atoi(getenv("ZKMI_NTT_DIGIT")) : 8u;
-        P.n_pass = (int)((L + maxbits - 1) / maxbits);
-        unsigned rem = L;
-        for (int i = 0; i < P.n_pass; i++) { unsigned li = (rem + (P.n_pass - i) - 1) / (P.n_pass - i); P.l[i] = li; rem -= li; }
-    }
+    P.n_pass = split.n_pass;
+    for (int i = 0; i < NTT_MAX_PASSES; i++) P.l[i] = split.l[i];
     const HE root = inverse ? R.wi[L] : R.w[L];
     P.log_lb = (L + 1) / 2;
     const size_t nlo = (size_t)1 << P.log_lb, nhi = (size_t)1 << (L - P.log_lb);
@@ -129,12 +133,10 @@ template <class C> static int ntt_run(int curve, const void* d_in, void* d_out, 
     // The 32-bit passes stay the default; the 29-bit ones are kept behind this switch with their own parity test.
     // r04 (three vector planes per tile, column-statement products): the 29-bit passes are faster up to 2^22 (2^16 0.0275 vs 0.033 ms, 2^20 0.151 vs 0.165,
     // 2^22 0.571 vs 0.618 forward) and slower from 2^24 (their 48-byte records between passes are 1.5 x the traffic: 2.66 vs 2.59 ms), profiles/r04_ntt29_ab.txt.
-    // ZKMI_NTT29=1 / 0 forces one form; unset: the 29-bit passes up to ZKMI_NTT29_MAX_LOG (default 22).
-    static const int env29 = getenv("ZKMI_NTT29") ? atoi(getenv("ZKMI_NTT29")) : -1;
-    static const unsigned max29 = getenv("ZKMI_NTT29_MAX_LOG") ? (unsigned)atoi(getenv("ZKMI_NTT29_MAX_LOG")) : 22u;
-    const bool use29 = env29 >= 0 ? env29 == 1 : L <= max29;
+    // ZKMI_NTT29=1 / 0 forces one form; unset: the 29-bit passes up to ZKMI_NTT29_MAX_LOG (default 22) — ntt_plan.hpp: ntt_use29.
+    const bool use29 = ntt_use29(L);
     uint32_t* d_rowinc = nullptr;
-    size_t rowoff[4] = {0, 0, 0, 0};
+    size_t rowoff[NTT_MAX_PASSES] = {};
     if (first) {
         size_t tot = 0;
         for (int i = 0; i < p; i++) { rowoff[i] = tot; tot += (size_t)1 << P->l[i]; }
@@ -189,7 +191,7 @@ template <class C> static int ntt_run(int curve, const void* d_in, void* d_out, 
     NttPassArgs a;
     a.log_n = L; a.n_pass = (uint32_t)p; a.log_lb = P->log_lb; a.T_lo = use29 ? P->T_lo29 : P->T_lo;
     a.in_len = in_len >= n ? 0 : in_len;
-    for (int i = 0; i < 4; i++) a.l[i] = P->l[i];
+    for (int i = 0; i < NTT_MAX_PASSES; i++) a.l[i] = P->l[i];
     unsigned logS = L;
     for (int i = 0; i < p - 1; i++) {
         logS -= P->l[i];
@@ -236,6 +238,20 @@ int ntt_power_tables(int curve, unsigned L, int inverse, const uint32_t** T_lo, 
     else if (curve == ZKMI_CURVE_BLS12381) { if ((int)L > fr_roots<Bls12381Fr>().s) return fail(ZKMI_ERR_UNSUPPORTED, "fft: log2(n) exceeds the 2-adicity of Fr"); ZK_TRY((get_plan<Bls12381Fr>(curve, L, inverse, &P))); }
     else return fail(ZKMI_ERR_INVALID, "unknown curve");
     *T_lo = P->T_lo; *T_hi = P->T_hi; *log_lb = P->log_lb; *n_inv = P->n_inv;
+    return ZKMI_OK;
+}
+
+// zkmi_ntt_plan_probe (include/zkmi_diag.h): what ntt_run would do for 2^log_n points, asked of the functions it decides with; no device
+int ntt_plan_probe(int curve, unsigned log_n, uint32_t* n_pass, uint32_t* l, int* limbs29) {
+    if (curve != ZKMI_CURVE_BN128 && curve != ZKMI_CURVE_BLS12381) return fail(ZKMI_ERR_INVALID, "unknown curve");
+    const int s = curve == ZKMI_CURVE_BN128 ? fr_roots<Bn254Fr>().s : fr_roots<Bls12381Fr>().s;
+    if (log_n > (unsigned)s) return fail(ZKMI_ERR_UNSUPPORTED, "fft: log2(n) exceeds the 2-adicity of Fr");
+    NttSplit split;
+    std::string why;
+    if (int rc = ntt_split_env(log_n, &split, &why)) return fail(rc, why);
+    if (n_pass) *n_pass = (uint32_t)split.n_pass;
+    if (l) for (int i = 0; i < NTT_MAX_PASSES; i++) l[i] = split.l[i];
+    if (limbs29) *limbs29 = ntt_use29(log_n) ? 1 : 0;
     return ZKMI_OK;
 }
 

@@ -918,6 +918,7 @@ int zkmi_ntt_padded_dev(int curve, const void* d_in, size_t in_len, void* d_out,
     if (!d_in || !d_out) return fail(ZKMI_ERR_INVALID, "null argument");
     return ntt_dev_padded_dispatch(curve, d_in, in_len, d_out, log_n, inverse);
 }
+int zkmi_ntt_plan_probe(int curve, unsigned log_n, uint32_t* n_pass, uint32_t* l, int* limbs29) { return ntt_plan_probe(curve, log_n, n_pass, l, limbs29); }
 int zkmi_ntt(int curve, zkmi_pages in, uint8_t* const* out_ptr, const size_t* out_len, int n_out, unsigned log_n, int inverse,
              const uint8_t* first, const uint8_t* inc) {
     ZK_TRY(require_ctx());

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/zkmi.h"
 #include "../../include/zkmi_diag.h"
+#include "ntt_plan.hpp"
 
 namespace zkmi {
 
@@ -33,13 +34,13 @@ struct DevBuf {
 struct NttPlan {
     unsigned log_n = 0;
     int n_pass = 0;
-    uint32_t l[4] = {0, 0, 0, 0};
+    uint32_t l[NTT_MAX_PASSES] = {};
     uint32_t log_lb = 0;
     uint32_t *T_lo = nullptr, *T_hi = nullptr, *T_hi_last = nullptr, *n_inv = nullptr;
-    uint32_t* LT[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t* LT[NTT_MAX_PASSES] = {};
     // the same tables in the R'-form of field29.cuh (t 2^261 mod r, packed canonical words) for the passes of ntt29.cuh; LT29 in bit-reversed order
     uint32_t *T_lo29 = nullptr, *T_hi29 = nullptr, *T_hi_last29 = nullptr, *n_inv29 = nullptr;
-    uint32_t* LT29[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t* LT29[NTT_MAX_PASSES] = {};
 };
 
 // Per-pipeline-slot resources. Two Groth16 proofs can be in flight (zkmi_groth16_submit_dev / _collect): the latency-bound tail of
@@ -115,6 +116,7 @@ int ntt_dev_dispatch(int curve, const void* d_in, void* d_out, unsigned log_n, i
 int ntt_dev_batch_dispatch(int curve, const void* d_in, size_t in_stride, void* d_out, size_t out_stride, unsigned batch, unsigned log_n, int inverse, const uint8_t* first,
                            const uint8_t* inc);
 int ntt_dev_padded_dispatch(int curve, const void* d_in, size_t in_len, void* d_out, unsigned log_n, int inverse);
+int ntt_plan_probe(int curve, unsigned log_n, uint32_t* n_pass, uint32_t* l, int* limbs29);      // host only: passes, digit widths (NTT_MAX_PASSES words), limb form
 // Fr.batchTo/FromMontgomery on up to four arrays in one launch (plonk.hip)
 int fr_convert_multi_dispatch(int curve, int op, const void* const* d_in, void* const* d_out, const size_t* ns, int count);
 int apply_key_dev_dispatch(int curve, const void* d_in, void* d_out, size_t n, const uint8_t* first, const uint8_t* inc);

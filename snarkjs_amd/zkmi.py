@@ -25,7 +25,7 @@ SYMBOLS = [
     "zkmi_dev_alloc", "zkmi_dev_free", "zkmi_memcpy_h2d", "zkmi_memcpy_d2h", "zkmi_memcpy_d2d", "zkmi_memset_dev",
     "zkmi_msm", "zkmi_release_bases", "zkmi_msm_dev", "zkmi_msm_sort_probe_dev", "zkmi_msm_stage_probe_dev", "zkmi_msm_set_window_bits", "zkmi_msm_accum_ms", "zkmi_msm_stats", "zkmi_msm_accum_additions", "zkmi_msm_table_build", "zkmi_msm_table_dev", "zkmi_msm_table_multi_dev", "zkmi_msm_table_multi_enqueue_dev", "zkmi_msm_table_multi_collect", "zkmi_msm_table_release", "zkmi_msm_table_info",
     "zkmi_ipc_export", "zkmi_ipc_open", "zkmi_ipc_close", "zkmi_peer_copy", "zkmi_peer_copy_async", "zkmi_peer_fence", "zkmi_groth16_key_curve", "zkmi_groth16_reset",
-    "zkmi_ntt", "zkmi_ntt_dev",
+    "zkmi_ntt", "zkmi_ntt_dev", "zkmi_ntt_plan_probe",
     "zkmi_fr_batch_apply_key", "zkmi_fr_batch_apply_key_dev", "zkmi_fr_batch", "zkmi_fr_batch_dev",
     "zkmi_groth16_join_abc", "zkmi_groth16_join_abc_dev",
     "zkmi_base_cache_stats", "zkmi_gen_bases_from_scalars_dev", "zkmi_group_fft", "zkmi_group_fft_dev", "zkmi_group_batch_apply_key", "zkmi_group_batch_apply_key_dev", "zkmi_group_convert", "zkmi_group_convert_dev", "zkmi_calibrate_box", "zkmi_calibrate_code_fetch", "zkmi_compact_code", "zkmi_groth16_load", "zkmi_groth16_prove", "zkmi_groth16_prove_dev", "zkmi_groth16_submit_dev", "zkmi_groth16_submit", "zkmi_groth16_sums_w_dev", "zkmi_groth16_collect", "zkmi_groth16_release", "zkmi_groth16_load_shard", "zkmi_groth16_sums_dev", "zkmi_groth16_chains_dev", "zkmi_groth16_sums_h_dev", "zkmi_groth16_finish", "zkmi_groth16_stage_ms",
@@ -216,6 +216,7 @@ def lib():
     L.zkmi_msm_accum_additions.restype = C.c_double
     L.zkmi_ntt.argtypes = [C.c_int, Pages, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_uint, C.c_int, u8p, u8p]
     L.zkmi_ntt_dev.argtypes = [C.c_int, vp, vp, C.c_uint, C.c_int, u8p, u8p]
+    L.zkmi_ntt_plan_probe.argtypes = [C.c_int, C.c_uint, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     L.zkmi_fr_batch_apply_key.argtypes = [C.c_int, Pages, C.POINTER(vp), C.POINTER(sz), C.c_int, sz, u8p, u8p]
     L.zkmi_fr_batch_apply_key_dev.argtypes = [C.c_int, vp, vp, sz, u8p, u8p]
     L.zkmi_fr_batch.argtypes = [C.c_int, C.c_int, Pages, C.POINTER(vp), C.POINTER(sz), C.c_int, sz]
