@@ -628,6 +628,24 @@ int zkmi_ptau_contribute_section(int curve, int group, zkmi_pages in, size_t n, 
                                  int n_lem_pages, uint8_t* const* c_ptr, const size_t* c_len, int n_c_pages, uint8_t* const* u_ptr, const size_t* u_len, int n_u_pages);
 int zkmi_blake2b512_partial(const uint8_t* const* chunks, const size_t* lens, int n, uint8_t* partial216);
 
+/* ---- the challenge / response round trip of phase 1 (src/powersoftau_challenge_contribute.js with applyKeyToChallengeSection of src/mpc_applykey.js,
+ * src/powersoftau_import.js) ------------------------------------------------------------------------------------------------------------------
+ * zkmi_ptau_challenge_section: one section of a response from one upload and one download. `in_u` holds n affine points of `group` in U form (a challenge
+ * file's bytes); first / inc are Montgomery Fr elements (host pointers). On the device: batchUtoLEM, out_i = (first * inc^i) * P_i, then batchLEMtoC
+ * (form == 0: half the size, what challengeContribute writes) or batchLEMtoU (form == 1, the reference's other branch). The multiplication runs in the slices
+ * of zkmi_ptau_contribute_section (zkmi_diag_set_ptau_slice applies), group 1 on its kernel, group 2 on the per-lane-scalar kernel of csrc/ptau_challenge.cuh.
+ * The points need not lie in the r-torsion; coordinates that are not on the curve give unspecified points.
+ * zkmi_ptau_import_section: one section of an import from one upload and two downloads. `in_c` holds n points in C form (a response file's bytes); on the
+ * device batchCtoLEM (the new file's bytes) and, on the resident result, batchLEMtoU (the bytes the next challenge hash takes). ZKMI_ERR_INVALID when some
+ * x has no point on the curve, as in zkmi_group_convert.
+ * Both: each output is a list of pages whose lengths add up to exactly n points. n == 0 returns ZKMI_OK and touches nothing. ZKMI_ERR_INVALID for an unknown
+ * curve, group or form, a null pointer, page totals that do not match n, and while a pipeline slot holds work in flight (the slot keeps its work);
+ * ZKMI_ERR_UNSUPPORTED for n >= 2^31. */
+int zkmi_ptau_challenge_section(int curve, int group, zkmi_pages in_u, size_t n, const uint8_t* first, const uint8_t* inc, uint8_t* const* out_ptr, const size_t* out_len,
+                                int n_out_pages, int form);
+int zkmi_ptau_import_section(int curve, int group, zkmi_pages in_c, size_t n, uint8_t* const* lem_ptr, const size_t* lem_len, int n_lem_pages, uint8_t* const* u_ptr,
+                             const size_t* u_len, int n_u_pages);
+
 /* curve.G1/G2.batchLEMtoU / batchUtoLEM / batchLEMtoC / batchCtoLEM (engine_batchconvert over wasmcurves' g1m_/g2m_batch*, min.js:1@128060;
  * callers src/powersoftau_import.js:159,221, src/powersoftau_contribute.js:145,176, src/powersoftau_export_challenge.js:72,
  * src/powersoftau_verify.js:358, src/mpc_applykey.js:64-70, src/zkey_export_bellman.js:36-83, src/zkey_new.js:103-115,373).

@@ -201,6 +201,10 @@ int zkmi_chacha_set_round_blocks(size_t blocks);
  * zkmi_diag_set_ptau_slice: points per slice of zkmi_ptau_contribute_section (0 restores the default of 2^20); the result does not depend on it. */
 int zkmi_diag_group_mul_each_dev(int curve, int group, const void* d_points, const void* d_scalars_normal, void* d_out, size_t n);
 int zkmi_diag_set_ptau_slice(size_t points);
+/* The G2 kernel of zkmi_ptau_challenge_section on its own (csrc/ptau_challenge.cuh): out_i = k_i * P_i for n affine LEM points of G2 (or of the twist outside
+ * it) and n scalars as above (device pointers; d_out must not overlap d_points). The refusals of zkmi_diag_group_mul_each_dev, in its words; it only enqueues
+ * on the library stream. For a point of order r every k below 2^255 gives (k mod r) P_i. */
+int zkmi_diag_group2_mul_each_dev(int curve, const void* d_points, const void* d_scalars_normal, void* d_out, size_t n);
 
 #ifdef __cplusplus
 }

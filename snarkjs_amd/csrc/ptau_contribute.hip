@@ -81,6 +81,11 @@ int pages_check(const char* what, uint8_t* const* ptr, const size_t* len, int n_
 }
 
 }  // namespace
+
+// for csrc/ptau_challenge.hip, whose section call cuts and runs its G1 slices as contribute_g1 does: the slice in force and the kernel on prepared scalars
+size_t ptau_slice_points() { return g_ptau_slice; }
+int ptau_mul_each_g1(int curve, const void* d_in, const void* d_scalars, void* d_out, size_t n) { return mul_each_dispatch(curve, d_in, d_scalars, d_out, n); }
+
 }  // namespace zkmi
 
 using namespace zkmi;

@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiPtauChallenge) uninstallPtauChallenge(curve);      // unregister(snarkjs): exportChallenge / challengeContribute / importResponse of registerAll(snarkjs, { ptauChallenge: true })
     if (curve && curve.__zkmiPtauContribute) uninstallPtauContribute(curve);    // unregister(snarkjs): newAccumulator / contribute / beacon of registerAll(snarkjs, { ptauContribute: true })
     if (curve && curve.__zkmiPtauPrepare) uninstallPtauPrepare(curve);          // unregister(snarkjs): preparePhase2 / convert of registerAll(snarkjs, { ptauPrepare: true })
     if (curve && curve.__zkmiPtauVerify) uninstallPtauVerify(curve);            // unregister(snarkjs): powersOfTau.verify of registerAll(snarkjs, { ptauVerify: true })
@@ -218,6 +219,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.ptauVerify) out.ptauVerify = installPtauVerify(snarkjs, options);
     if (options && options.ptauPrepare) out.ptauPrepare = installPtauPrepare(snarkjs, options);
     if (options && options.ptauContribute) out.ptauContribute = installPtauContribute(snarkjs, options);
+    if (options && options.ptauChallenge) out.ptauChallenge = installPtauChallenge(snarkjs, options);
     return out;
 }
 
@@ -483,6 +485,66 @@ function uninstallPtauContribute(snarkjs) {
     delete snarkjs.__zkmiPtauContribute;
 }
 
+// ---- powersOfTau.exportChallenge / challengeContribute / importResponse on the device (opt-in: registerAll(snarkjs, { ptauChallenge: true })) -----------------
+// A section is one call (js/powersoftau_challenge_native.js). Same arguments, the same draw of 64 bytes, the same bytes in the new file, the same result
+// (the challenge hash, undefined, the next challenge hash) and the reference's errors. Handed to the saved reference function: whatever the driver marks
+// handOver (a file that is not well-formed, power 0 in importResponse, an empty entropy, a section beyond one buffer, ...).
+function installPtauChallenge(snarkjs, options) {
+    if (snarkjs.__zkmiPtauChallenge) return snarkjs.__zkmiPtauChallenge;
+    const chN = require("./powersoftau_challenge_native.js");
+    const saved = { exportChallenge: snarkjs.powersOfTau.exportChallenge, challengeContribute: snarkjs.powersOfTau.challengeContribute, importResponse: snarkjs.powersOfTau.importResponse };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const dev = options && options.dev;
+    const logOf = (logger) => (level, text) => { if (logger && typeof logger[level] === "function") logger[level](text); };
+    const nameOf = (src) => (typeof src === "string" ? src : (src && src.fileName));
+    function store(target, raw, what) {
+        if (typeof target === "string") require("fs").writeFileSync(target, raw);
+        else if (target && target.type === "file") require("fs").writeFileSync(target.fileName, raw);
+        else if (target && target.type === "mem") target.data = raw;
+        else throw new Error(what + ": expected a path or a fastfile descriptor for the new file");
+    }
+    // run the driver; null: the call goes to the saved function
+    async function attempt(f, onThrow) {
+        try { return await f(); } catch (e) {
+            if (!(e instanceof chN.ChallengeRefusal)) throw e;
+            if (e.handOver) return null;
+            if (onThrow) onThrow(e);
+            throw new Error(e.message);
+        }
+    }
+    async function exportChallenge(pTauFilename, challengeFilename, logger) {
+        const res = await attempt(() => chN.exportChallenge(pTauFilename, { addon, dev, log: logOf(logger), fileName: nameOf(pTauFilename) }),
+                                  (e) => { if (e.challenge) store(challengeFilename, e.challenge, "powersOfTau.exportChallenge"); });
+        if (res === null) return saved.exportChallenge(pTauFilename, challengeFilename, logger);
+        store(challengeFilename, res.challenge, "powersOfTau.exportChallenge");
+        return res.challengeHash;
+    }
+    async function challengeContribute(curve, challengeFilename, responseFileName, entropy, logger) {
+        if (!entropy) return saved.challengeContribute(curve, challengeFilename, responseFileName, entropy, logger);
+        const random64 = new Uint8Array(64);
+        if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random64); else require("crypto").randomFillSync(random64);
+        const res = await attempt(() => chN.challengeContribute(curve, challengeFilename, entropy, { addon, dev, random64, log: logOf(logger) }));
+        // the saved function draws its own 64 bytes: a pinned stream differs from the reference's by this one draw, on calls the driver does not take
+        if (res === null) return saved.challengeContribute(curve, challengeFilename, responseFileName, entropy, logger);
+        store(responseFileName, res.response, "powersOfTau.challengeContribute");
+    }
+    async function importResponse(oldPtauFilename, contributionFilename, newPTauFilename, name, importPoints, logger) {
+        const res = await attempt(() => chN.importResponse(oldPtauFilename, contributionFilename, name, importPoints, { addon, dev, log: logOf(logger) }));
+        if (res === null) return saved.importResponse(oldPtauFilename, contributionFilename, newPTauFilename, name, importPoints, logger);
+        store(newPTauFilename, res.ptau, "powersOfTau.importResponse");
+        return res.nextChallenge;
+    }
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, { exportChallenge, challengeContribute, importResponse }));
+    snarkjs.__zkmiPtauChallenge = { saved };
+    return snarkjs.__zkmiPtauChallenge;
+}
+function uninstallPtauChallenge(snarkjs) {
+    if (!snarkjs.__zkmiPtauChallenge) return;
+    snarkjs.powersOfTau = Object.freeze(Object.assign({}, snarkjs.powersOfTau, snarkjs.__zkmiPtauChallenge.saved));
+    delete snarkjs.__zkmiPtauChallenge;
+}
+
 // ---- plonk.setup on the device (opt-in: registerAll(snarkjs, { plonkSetup: true }); { setup: true } stays Groth16 only) ------------------------------
 // plonk.setup reaches the device through the patched curve methods alone for its transforms and multiexps; the gate lowering, the permutation, the Lagrange
 // section and the selector buffers stay single-threaded JavaScript (src/plonk_setup.js). Replaced through the writable PROPERTY snarkjs.plonk: same
@@ -625,4 +687,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, installPtauChallenge, uninstallPtauChallenge, loadAddon };

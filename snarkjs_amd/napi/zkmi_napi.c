@@ -460,6 +460,44 @@ static napi_value js_ptau_contribute_section(napi_env env, napi_callback_info in
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
+/* ---- the challenge / response round trip of phase 1 (js/powersoftau_challenge_native.js)
+ * ptauChallengeSection(curve, group, pointsU, n, first, inc, form) -> Uint8Array: (first * inc^i) P_i for the n U-form points of a challenge section, in C form
+ * (form 0: n * sG / 2 bytes) or in U form (form 1: n * sG bytes). first, inc: 32-byte Montgomery Fr elements.
+ * ptauImportSection(curve, group, pointsC, n) -> Uint8Array: the n C-form points of a response section as LEM (n * sG bytes, the file's) and U (n * sG, the next
+ * challenge hash's), back to back. */
+static napi_value js_ptau_challenge_section(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    int32_t curve, group, form; double n;
+    pages_t in, f, k;
+    if (get_i32(env, argv[0], &curve) || get_i32(env, argv[1], &group) || (group != 1 && group != 2) || get_pages(env, argv[2], &in) || get_f64(env, argv[3], &n) || n < 0 ||
+        n > 2147483647.0 || get_pages(env, argv[4], &f) || f.n != 1 || f.len[0] != 32 || get_pages(env, argv[5], &k) || k.n != 1 || k.len[0] != 32 || get_i32(env, argv[6], &form) ||
+        (form != 0 && form != 1) || !n8q_of_curve(curve)) BAD_ARG();
+    const size_t sg = 2 * (size_t)group * (size_t)n8q_of_curve(curve), b = (size_t)n * sg, ob = form ? b : b / 2;
+    uint8_t* out;
+    napi_value res = new_u8(env, ob, &out);
+    if (!res) BAD_ARG();
+    uint8_t* op[1] = {out};
+    const size_t ol[1] = {ob};
+    int rc = ZK_CALL(zkmi_ptau_challenge_section(curve, group, as_zk(&in), (size_t)n, f.ptr[0], k.ptr[0], op, ol, 1, form));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
+static napi_value js_ptau_import_section(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    int32_t curve, group; double n;
+    pages_t in;
+    if (get_i32(env, argv[0], &curve) || get_i32(env, argv[1], &group) || (group != 1 && group != 2) || get_pages(env, argv[2], &in) || get_f64(env, argv[3], &n) || n < 0 ||
+        n > 2147483647.0 || !n8q_of_curve(curve)) BAD_ARG();
+    const size_t sg = 2 * (size_t)group * (size_t)n8q_of_curve(curve), b = (size_t)n * sg;
+    uint8_t* out;
+    napi_value res = new_u8(env, 2 * b, &out);
+    if (!res) BAD_ARG();
+    uint8_t* lp[1] = {out}; uint8_t* up[1] = {out + b};
+    const size_t ll[1] = {b}, ul[1] = {b};
+    int rc = ZK_CALL(zkmi_ptau_import_section(curve, group, as_zk(&in), (size_t)n, lp, ll, 1, up, ul, 1));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* blake2b512Partial(chunks) -> Uint8Array(216): misc.toPartialHash of a fresh hasher after one update per chunk (an array of at most 256 Uint8Arrays) */
 static napi_value js_blake2b512_partial(napi_env env, napi_callback_info info) {
     ARGS(1);
@@ -1433,7 +1471,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
         {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
-        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial},
+        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial}, {"ptauChallengeSection", js_ptau_challenge_section}, {"ptauImportSection", js_ptau_import_section},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},
         {"devAlloc", js_dev_alloc}, {"devFree", js_dev_free}, {"memcpyH2D", js_memcpy_h2d}, {"memcpyD2H", js_memcpy_d2h},

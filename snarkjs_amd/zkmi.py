@@ -48,6 +48,7 @@ SYMBOLS = [
     "zkmi_chacha_block_host", "zkmi_chacha_struct_words_host", "zkmi_chacha_fr_host", "zkmi_chacha_fr_compact_host", "zkmi_chacha_set_round_blocks",
     "zkmi_ptau_section_check", "zkmi_blake2b512_resume", "zkmi_ptau_key_from_seed", "zkmi_ptau_lagrange_section", "zkmi_ptau_lagrange_dev",
     "zkmi_ptau_contribute_section", "zkmi_blake2b512_partial", "zkmi_diag_group_mul_each_dev", "zkmi_diag_set_ptau_slice",
+    "zkmi_ptau_challenge_section", "zkmi_ptau_import_section", "zkmi_diag_group2_mul_each_dev",
 ]
 
 
@@ -341,6 +342,9 @@ def lib():
     L.zkmi_blake2b512_partial.argtypes = [C.POINTER(vp), C.POINTER(sz), C.c_int, u8p]
     L.zkmi_diag_group_mul_each_dev.argtypes = [C.c_int, C.c_int, vp, vp, vp, sz]
     L.zkmi_diag_set_ptau_slice.argtypes = [sz]
+    L.zkmi_ptau_challenge_section.argtypes = [C.c_int, C.c_int, Pages, sz, u8p, u8p, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_int]
+    L.zkmi_ptau_import_section.argtypes = [C.c_int, C.c_int, Pages, sz] + [C.POINTER(vp), C.POINTER(sz), C.c_int] * 2
+    L.zkmi_diag_group2_mul_each_dev.argtypes = [C.c_int, vp, vp, vp, sz]
     _lib = _Locked(L)
     return _lib
 
