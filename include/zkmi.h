@@ -659,6 +659,27 @@ int zkmi_ptau_import_section(int curve, int group, zkmi_pages in_c, size_t n, ui
 int zkmi_group_convert(int curve, int group, int kind, zkmi_pages in, uint8_t* const* out_ptr, const size_t* out_len, int n_out_pages, size_t n);
 int zkmi_group_convert_dev(int curve, int group, int kind, const void* d_in, void* d_out, size_t n);
 
+/* ---- witness check: wtns.check (src/wtns_check.js) ------------------------------------------------------------------------------------
+ * Constraint i holds iff evalA * evalB == evalC in Fr; an evaluation is the sum of coef * w[signal] over the DISTINCT signals of the combination, with
+ * the LAST coefficient the file gives for a signal. Coefficients and witness values are any 256-bit little-endian value, taken mod r; w[0] need not be 1;
+ * a zero coefficient and an empty combination are legal.
+ *   zkmi_r1cs_load     `constraints` = r1cs section 2 as it lies in the file (per constraint three combinations, each u32 n then n x (u32 signal, 32-byte
+ *                      coefficient)); bytes after the last constraint are ignored. The term counts are read on the host, the section goes up once and the
+ *                      resident layout is built on the device (csrc/r1cs_check.cuh). ZKMI_ERR_INVALID: an unknown curve, a null pointer, cache_key 0, a
+ *                      section that ends inside a constraint, a signal id >= n_vars, another r1cs resident under the key (the same one: ZKMI_OK, nothing is
+ *                      done). ZKMI_ERR_UNSUPPORTED: 3 * n_constraints >= 2^31, 2^32 terms or more. n_constraints == 0 loads.
+ *   zkmi_r1cs_check    n_witnesses witnesses of n_vars x 32 bytes each, one after the other in host memory (wtns section 2); witness_len must be
+ *                      n_witnesses * n_vars * 32. first_bad[k] = index of the first constraint witness k fails, 0xFFFFFFFF when it satisfies all (with
+ *                      n_constraints == 0: always). A large batch is cut into passes that fit the work memory. ZKMI_ERR_INVALID: cache_key 0, no r1cs
+ *                      resident under the key, a null pointer, a wrong witness_len; the resident r1cs is left as it was.
+ *   zkmi_r1cs_check_dev the same for witnesses already in device memory (a resident prover gating on the verdict); first_bad is host memory.
+ *   zkmi_r1cs_release  frees the layout and its work memory (an unknown key: ZKMI_OK).
+ * All of them use the active pipeline slot's stream and compute no MSM: not refused while a slot holds work in flight. Complete on return. */
+int zkmi_r1cs_load(int curve, zkmi_pages constraints, uint32_t n_constraints, uint32_t n_vars, uint64_t cache_key);
+int zkmi_r1cs_check(uint64_t cache_key, const uint8_t* witnesses, size_t witness_len, uint32_t n_witnesses, uint32_t* first_bad);
+int zkmi_r1cs_check_dev(uint64_t cache_key, const void* d_witnesses, size_t witness_len, uint32_t n_witnesses, uint32_t* first_bad);
+int zkmi_r1cs_release(uint64_t cache_key);
+
 
 /* ---- utilities --------------------------------------------------------------------------------------------------- */
 /* Page-lock caller-owned host memory for device transfers (hipHostRegister): shared-memory regions through which the processes of a

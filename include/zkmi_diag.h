@@ -205,6 +205,9 @@ int zkmi_diag_set_ptau_slice(size_t points);
  * it) and n scalars as above (device pointers; d_out must not overlap d_points). The refusals of zkmi_diag_group_mul_each_dev, in its words; it only enqueues
  * on the library stream. For a point of order r every k below 2^255 gives (k mod r) P_i. */
 int zkmi_diag_group2_mul_each_dev(int curve, const void* d_points, const void* d_scalars_normal, void* d_out, size_t n);
+/* Bytes of work memory one pass of zkmi_r1cs_check(_dev) may take (0 restores the default of 4 GiB): a batch of witnesses is cut into passes that fit, one
+ * witness at the least; the verdicts do not depend on it. */
+int zkmi_diag_set_r1cs_budget(size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,7 @@ function register(curve, options) {
 
 // Undo register(): restore the reference WASM entry points (used by A/B parity tests).
 function unregister(curve) {
+    if (curve && curve.__zkmiWtnsCheck) uninstallWtnsCheck(curve);              // unregister(snarkjs): wtns.check of registerAll(snarkjs, { wtnsCheck: true })
     if (curve && curve.__zkmiPtauChallenge) uninstallPtauChallenge(curve);      // unregister(snarkjs): exportChallenge / challengeContribute / importResponse of registerAll(snarkjs, { ptauChallenge: true })
     if (curve && curve.__zkmiPtauContribute) uninstallPtauContribute(curve);    // unregister(snarkjs): newAccumulator / contribute / beacon of registerAll(snarkjs, { ptauContribute: true })
     if (curve && curve.__zkmiPtauPrepare) uninstallPtauPrepare(curve);          // unregister(snarkjs): preparePhase2 / convert of registerAll(snarkjs, { ptauPrepare: true })
@@ -220,7 +221,41 @@ async function registerAll(snarkjs, options) {
     if (options && options.ptauPrepare) out.ptauPrepare = installPtauPrepare(snarkjs, options);
     if (options && options.ptauContribute) out.ptauContribute = installPtauContribute(snarkjs, options);
     if (options && options.ptauChallenge) out.ptauChallenge = installPtauChallenge(snarkjs, options);
+    if (options && options.wtnsCheck) out.wtnsCheck = installWtnsCheck(snarkjs, options);
     return out;
+}
+
+// ---- wtns.check on the device (opt-in: registerAll(snarkjs, { wtnsCheck: true })) ---------------------------------------------------------------------------
+// The reference's check is one JavaScript loop over the constraints that no curve method sees, so like the fused provers it is replaced through the writable
+// PROPERTY snarkjs.wtns (js/wtns_check_native.js). Same arguments (paths, fastfile descriptors, in-memory files), verdict and info / warn lines; a bad witness
+// with no logger throws the reference's TypeError. Handed to the saved reference function, before a line is logged or the device is touched: every input the
+// reference refuses or reads beyond a buffer for (js/wtns_check_native.js lists them). options.dev replaces the device calls.
+function installWtnsCheck(snarkjs, options) {
+    if (snarkjs.__zkmiWtnsCheck) return snarkjs.__zkmiWtnsCheck;
+    const wtnsN = require("./wtns_check_native.js");
+    const saved = { check: snarkjs.wtns.check };
+    let dev = options && options.dev;
+    if (!dev) {
+        const addon = (options && options.addon) || loadAddon();
+        addon.init(options && options.device !== undefined ? options.device : 0);
+        dev = wtnsN.deviceOf(addon);
+    }
+    async function check(r1csFilename, wtnsFilename, logger) {
+        try {
+            return await wtnsN.check(r1csFilename, wtnsFilename, logger, { dev });
+        } catch (e) {
+            if (e instanceof wtnsN.WtnsRefusal && e.handOver) return saved.check(r1csFilename, wtnsFilename, logger);
+            throw e;
+        }
+    }
+    snarkjs.wtns = Object.freeze(Object.assign({}, snarkjs.wtns, { check }));
+    snarkjs.__zkmiWtnsCheck = { saved };
+    return snarkjs.__zkmiWtnsCheck;
+}
+function uninstallWtnsCheck(snarkjs) {
+    if (!snarkjs.__zkmiWtnsCheck) return;
+    snarkjs.wtns = Object.freeze(Object.assign({}, snarkjs.wtns, snarkjs.__zkmiWtnsCheck.saved));
+    delete snarkjs.__zkmiWtnsCheck;
 }
 
 // ---- zKey.newZKey on the device (opt-in: registerAll(snarkjs, { setup: true })) ---------------------------------------------------------------------
@@ -687,4 +722,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, installPtauChallenge, uninstallPtauChallenge, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, installPtauChallenge, uninstallPtauChallenge, installWtnsCheck, uninstallWtnsCheck, loadAddon };

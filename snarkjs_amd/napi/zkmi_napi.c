@@ -523,6 +523,32 @@ static napi_value js_blake2b_resume(napi_env env, napi_callback_info info) {
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
+/* ---- the witness check (js/wtns_check_native.js)
+ * r1csLoad(curve, constraints, nConstraints, nVars, key): zkmi_r1cs_load of r1cs section 2 (Uint8Array | Array<Uint8Array>) under `key` (a positive integer below 2^53)
+ * r1csCheck(key, witnesses, nWitnesses) -> Uint8Array(4 nWitnesses): first_bad as little-endian 32-bit words, 0xFFFFFFFF for a witness that satisfies every constraint;
+ * `witnesses` holds nWitnesses x nVars x 32 bytes. The layout is released with call("zkmi_r1cs_release", key). */
+static napi_value js_r1cs_load(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    int32_t curve; double n_c, n_vars, key;
+    pages_t c;
+    if (get_i32(env, argv[0], &curve) || get_pages(env, argv[1], &c) || get_f64(env, argv[2], &n_c) || n_c < 0 || n_c > 4294967295.0 || get_f64(env, argv[3], &n_vars) || n_vars < 0 ||
+        n_vars > 4294967295.0 || get_f64(env, argv[4], &key) || key < 1 || key > 9007199254740992.0) BAD_ARG();
+    int rc = ZK_CALL(zkmi_r1cs_load(curve, as_zk(&c), (uint32_t)n_c, (uint32_t)n_vars, (uint64_t)key));
+    if (rc) return throw_zkmi(env, rc);
+    return NULL;
+}
+static napi_value js_r1cs_check(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    double key, n;
+    pages_t w;
+    if (get_f64(env, argv[0], &key) || key < 0 || key > 9007199254740992.0 || get_pages(env, argv[1], &w) || w.n != 1 || get_f64(env, argv[2], &n) || n < 0 || n > 16777216.0) BAD_ARG();
+    uint8_t* out;
+    napi_value res = new_u8(env, 4 * (size_t)n, &out);
+    if (!res) BAD_ARG();
+    int rc = ZK_CALL(zkmi_r1cs_check((uint64_t)key, w.len[0] ? w.ptr[0] : NULL, w.len[0], (uint32_t)n, (uint32_t*)out));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* groupConvert(curve, group, kind, in, out, n): G.batchLEMtoU (0) / batchUtoLEM (1) / batchLEMtoC (2) / batchCtoLEM (3) */
 static napi_value js_group_convert(napi_env env, napi_callback_info info) {
     ARGS(6);
@@ -1222,6 +1248,7 @@ static const struct { const char* name; const char* sig; } g_call_table[] = {
     {"zkmi_chacha_words_dev", "b32 i d i"}, {"zkmi_chacha_fr_dev", "i b32 d i B8"},
     /* the sequential generator on the host (include/zkmi_diag.h): what tests put in the kernels' place */
     {"zkmi_chacha_struct_words_host", "b32 i b*3:4 i"}, {"zkmi_chacha_fr_host", "i b32 b*3:32 i B8"},
+    {"zkmi_r1cs_release", "i"},
 };
 static void* zk_lib_handle(void) {
     static void* h = NULL;
@@ -1471,7 +1498,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
         {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
-        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial}, {"ptauChallengeSection", js_ptau_challenge_section}, {"ptauImportSection", js_ptau_import_section},
+        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial}, {"ptauChallengeSection", js_ptau_challenge_section}, {"ptauImportSection", js_ptau_import_section}, {"r1csLoad", js_r1cs_load}, {"r1csCheck", js_r1cs_check},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},
         {"devAlloc", js_dev_alloc}, {"devFree", js_dev_free}, {"memcpyH2D", js_memcpy_h2d}, {"memcpyD2H", js_memcpy_d2h},

@@ -195,6 +195,100 @@ def square_chain(curve, n_c, x0=3, b=5):
     return n_c + 2, 1, 1, cons, wit
 
 
+def write_wtns(curve, values, prime=None):
+    """bytes of a .wtns file (version 2): values are non-negative integers below 2^256, written as they are (a value of r or more stays one)"""
+    q = R[curve] if prime is None else prime
+    head = struct.pack("<I", 32) + q.to_bytes(32, "little") + struct.pack("<I", len(values))
+    body = b"".join(int(v).to_bytes(32, "little") for v in values)
+    out = bytearray(b"wtns" + struct.pack("<II", 2, 2))
+    for typ, sec in ((1, head), (2, body)):
+        out += struct.pack("<IQ", typ, len(sec)) + sec
+    return bytes(out)
+
+
+def lc_value(lc, wit, r):
+    """a combination as wtns.check evaluates it: the LAST coefficient the list gives for a signal, each signal once"""
+    last = {}
+    for s, c in lc:
+        last[s] = c
+    return sum((c % r) * (wit[s] % r) for s, c in last.items()) % r
+
+
+def satisfiable_circuit(curve, n_c, seed=0x5a7, n_free=12, rows=None, dups=False, wide=False, w0=1, tail=False):
+    """n_c SATISFIED constraints and their witness -> (n_vars, n_outputs, n_pub_inputs, constraints, witness as a list of integers).
+    A and B are random combinations of signals whose value is known; C is, in turn, one free signal (with random known terms beside it) whose value is
+    solved from A * B, a lone constant on signal 0, or empty with the last coefficient of A (or of B) solved so that the combination evaluates to 0.
+      rows   {(constraint, matrix): terms}: that combination gets exactly so many terms (matrix 0 = A, 1 = B, 2 = C), over distinct signals
+      tail   heavy-tailed lengths for A where rows says nothing: short ones, and with probability `tail` (True: 0.1) one of 10^2 - 10^3 terms
+      dups   some combinations name a signal twice, adjacent and apart, with an earlier coefficient that is NOT the one that counts
+      wide   some coefficients are written as c + r or c + k r below 2^256, some witness values as v + r
+      w0     value of signal 0 (wtns.check does not ask for 1)"""
+    r = R[curve]
+    rng = random.Random(seed + len(curve))
+    rows = dict(rows or {})
+    p_long = 0.1 if tail is True else float(tail)
+    longest = max(list(rows.values()) + [0])
+    n_free = max(n_free, longest + 2, 1100 if tail else 0)
+    wit = [w0 % r] + [rng.randrange(1, r) for _ in range(n_free - 1)]
+    cons = []
+
+    def coef():
+        k = rng.random()
+        c = (1 if rng.random() < 0.5 else r - 1) if k < 0.5 else (rng.randrange(2, 1 << 16) if k < 0.7 else (1 << rng.randrange(1, 253) if k < 0.8 else rng.randrange(1, r)))
+        if wide and rng.random() < 0.3:
+            c += r * rng.randrange(1, ((1 << 256) - 1 - c) // r + 1)
+        return c
+
+    def combo(n, known, must=None):
+        sigs = rng.sample(range(known), min(n, known))
+        if must is not None and must not in sigs and sigs:
+            sigs[-1] = must
+        return [(s, coef()) for s in sigs]
+
+    def with_dups(lc, known):
+        """the same evaluation, with a stale coefficient in front of the one that counts: adjacent for the first term, apart for the last"""
+        if len(lc) < 2:
+            return lc
+        (s0, c0), (s1, c1) = lc[0], lc[-1]
+        return [(s0, (c0 + 1 + rng.randrange(r - 2)) % r), (s0, c0), (s1, (c1 + 1 + rng.randrange(r - 2)) % r)] + lc[1:-1] + [(s1, c1)]
+
+    for i in range(n_c):
+        known = len(wit)
+        la = rows.get((i, 0), (rng.choice([1, 1, 1, 2, 3]) if rng.random() >= p_long else rng.randrange(100, 1000)) if tail else rng.randrange(1, 4))
+        lb, lcn = rows.get((i, 1), rng.randrange(1, 3)), rows.get((i, 2))
+        kind = i % 3 if lcn is None else (0 if lcn > 0 else 2)
+        a, b = combo(la, known), combo(lb, known)
+        if kind == 2:                                                    # C empty: A (or, every other time, B) is made to evaluate to 0
+            side = a if (i // 3) % 2 == 0 or not b else b
+            if side:
+                s = next((t for t, _ in reversed(side) if wit[t] % r), None)
+                if s is None:
+                    kind = 1
+                else:
+                    rest = [(t, c) for t, c in side if t != s]
+                    side[:] = rest + [(s, (-lc_value(rest, wit, r) * pow(wit[s], -1, r)) % r)]
+            c = []
+        if kind == 1:                                                    # C: a lone constant on signal 0
+            if wit[0] % r == 0:
+                kind = 0
+            else:
+                c = [(0, lc_value(a, wit, r) * lc_value(b, wit, r) * pow(wit[0], -1, r) % r)]
+        if kind == 0:                                                    # C: one free signal solved from the rest
+            rest = combo((lcn if lcn is not None else rng.randrange(1, 4)) - 1, known)
+            k = rng.randrange(1, r)
+            wit.append((lc_value(a, wit, r) * lc_value(b, wit, r) - lc_value(rest, wit, r)) * pow(k, -1, r) % r)
+            c = rest + [(known, k)]
+            rng.shuffle(c)
+        if dups and i % 2 == 0:
+            a, b, c = with_dups(a, known), (with_dups(b, known) if i % 4 == 0 else b), (with_dups(c, known) if kind == 0 else c)
+        cons.append((a, b, c))
+    if wide:
+        wit = [v + r if v + r < 1 << 256 and rng.random() < 0.3 else v for v in wit]
+    for a, b, c in cons:
+        assert lc_value(a, wit, r) * lc_value(b, wit, r) % r == lc_value(c, wit, r)
+    return len(wit), 1, 1, cons, wit
+
+
 def fflonk_quirks_circuit(curve):
     """FFLONK setup fixture (src/r1cs_constraint_processor.js): every case of the lowering in 14 rows (domain 16), nPublic = 0. Each of the first four
     constraints gives one row; the multiplication gives ten: its A, B and C each hold five terms, the constant and four signals, so each folds
