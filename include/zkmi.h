@@ -548,6 +548,19 @@ int zkmi_phase2_key_from_seed(int curve, const uint32_t* seed8, uint8_t* prv_key
 int zkmi_phase2_hash_to_g2(int curve, const uint8_t* transcript64, uint8_t* g2_sp);
 int zkmi_point_mul(int curve, int group, const uint8_t* affine, const uint8_t* k_mont, uint8_t* out_affine);
 
+/* ---- the H basis change of a Bellman-format phase-2 round trip (src/zkey_export_bellman.js:43-52, src/zkey_import_bellman.js:133-142) --
+ * G1 only; n = 2^log_n = the key's domainSize, w = Fr.w[log_n + 1]. One upload, log_n + 3 or + 4 launches over one work array, one download.
+ *   direction 0 (export): `in` holds n affine LEM points (section 9 of the key, all-zero = infinity); out = n - 1 points in the reference's uncompressed
+ *     big-endian form (toRprUncompressed / batchLEMtoU, all-zero = infinity): point i = (-2 w^i) * G1.fft(in)_i. Index n - 1 is not computed.
+ *   direction 1 (import): `in` holds n - 1 uncompressed points; out = n affine LEM points = G1.ifft([(-(1/2) w^-j) * P_j ..., infinity]), the 1 / n of the
+ *     inverse transform folded into the one scalar of each point.
+ * Export followed by import is not the identity: the coefficient export drops comes back as zero. The output pages' lengths add up to exactly the points
+ * written. ZKMI_ERR_UNSUPPORTED for log_n < 1, log_n + 1 > Fr.s (28 on BN254, 32 on BLS12-381) and log_n > 28; ZKMI_ERR_INVALID for an unknown curve or
+ * direction, a null pointer, page totals that do not match, or a pipeline slot with work in flight. The _dev twin runs on resident buffers (16-byte
+ * aligned; d_in and d_out distinct). */
+int zkmi_bellman_h_section(int curve, zkmi_pages in, unsigned log_n, int direction, uint8_t* const* out_ptr, const size_t* out_len, int n_out_pages);
+int zkmi_bellman_h_section_dev(int curve, const void* d_in, void* d_out, unsigned log_n, int direction);
+
 /* ---- verification of a Groth16 phase-2 key (src/zkey_verify_frominit.js, src/zkey_verify_fromr1cs.js) --------------------------------
  * The reference's generator by position. ChaCha(seed8) is ffjavascript's: the keystream in nextU32 order is word j = word j % 16 of block j / 16.
  * zkmi_chacha_words_dev: d_out[j] = keystream word first_word + j for j < n_words (32-bit words; first_word need not be a multiple of 16).

@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, "build" + ("_" + VARIANT if VARIANT else ""))
 LIB = os.path.join(HERE, "libzkmi" + ("_" + VARIANT if VARIANT else "") + ".so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"] + os.environ.get("ZKMI_EXTRA_FLAGS", "").split()
-UNITS = ["zkmi_api.hip", "ntt.hip", "msm_sort.hip", "msm_bn254.hip", "msm_bls12381.hip", "groth16.hip", "plonk.hip", "gfft.hip", "gconv.hip", "calib.hip", "peer.hip", "groth16_verify.hip", "plonk_verify.hip", "fflonk_verify.hip", "groth16_setup.hip", "plonk_setup.hip", "fflonk_setup.hip", "group_scale.hip", "phase2_verify.hip", "ptau_verify.hip", "ptau_lagrange.hip", "ptau_contribute.hip", "ptau_challenge.hip", "r1cs_check.hip"]
+UNITS = ["zkmi_api.hip", "ntt.hip", "msm_sort.hip", "msm_bn254.hip", "msm_bls12381.hip", "groth16.hip", "plonk.hip", "gfft.hip", "gconv.hip", "calib.hip", "peer.hip", "groth16_verify.hip", "plonk_verify.hip", "fflonk_verify.hip", "groth16_setup.hip", "plonk_setup.hip", "fflonk_setup.hip", "group_scale.hip", "phase2_verify.hip", "ptau_verify.hip", "ptau_lagrange.hip", "ptau_contribute.hip", "ptau_challenge.hip", "r1cs_check.hip", "bellman.hip"]
 
 
 def _stale(target, deps):

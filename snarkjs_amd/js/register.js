@@ -192,6 +192,7 @@ function unregister(curve) {
     if (curve && curve.__zkmiPtauContribute) uninstallPtauContribute(curve);    // unregister(snarkjs): newAccumulator / contribute / beacon of registerAll(snarkjs, { ptauContribute: true })
     if (curve && curve.__zkmiPtauPrepare) uninstallPtauPrepare(curve);          // unregister(snarkjs): preparePhase2 / convert of registerAll(snarkjs, { ptauPrepare: true })
     if (curve && curve.__zkmiPtauVerify) uninstallPtauVerify(curve);            // unregister(snarkjs): powersOfTau.verify of registerAll(snarkjs, { ptauVerify: true })
+    if (curve && curve.__zkmiBellman) uninstallBellman(curve);                  // unregister(snarkjs): exportBellman / bellmanContribute / importBellman of registerAll(snarkjs, { bellman: true })
     if (curve && curve.__zkmiPhase2Verify) uninstallPhase2Verify(curve);    // unregister(snarkjs): verifyFromInit / verifyFromR1cs of registerAll(snarkjs, { phase2Verify: true })
     if (curve && curve.__zkmiPhase2) uninstallPhase2(curve);            // unregister(snarkjs): contribute / beacon of registerAll(snarkjs, { phase2: true }), before the setup gives the namespace back
     if (curve && curve.__zkmiSetup) uninstallSetup(curve);              // unregister(snarkjs): the setup replacement installed by registerAll(snarkjs, { setup: true })
@@ -217,6 +218,7 @@ async function registerAll(snarkjs, options) {
     if (options && options.fflonkSetup) out.fflonkSetup = installFflonkSetup(snarkjs, options);
     if (options && options.phase2) out.phase2 = installPhase2(snarkjs, options);
     if (options && options.phase2Verify) out.phase2Verify = installPhase2Verify(snarkjs, options);
+    if (options && options.bellman) out.bellman = installBellman(snarkjs, options);
     if (options && options.ptauVerify) out.ptauVerify = installPtauVerify(snarkjs, options);
     if (options && options.ptauPrepare) out.ptauPrepare = installPtauPrepare(snarkjs, options);
     if (options && options.ptauContribute) out.ptauContribute = installPtauContribute(snarkjs, options);
@@ -354,6 +356,67 @@ function uninstallPhase2(snarkjs) {
     if (!snarkjs.__zkmiPhase2) return;
     snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiPhase2.saved));
     delete snarkjs.__zkmiPhase2;
+}
+
+// ---- zKey.exportBellman / bellmanContribute / importBellman on the device (opt-in: registerAll(snarkjs, { bellman: true })) ---------------------------------
+// Through the patched curve methods the H basis change of these calls does not reach the device (G.fft / G.ifft / G.batchApplyKey with a jacobian form are
+// forwarded to WASM); here it is one call each way (js/groth16_bellman_native.js). Same arguments, the same draw of 64 bytes, the same bytes in the new file,
+// the same result (undefined, the contribution hash, true) and logger lines; importBellman returns false with the reference's logger.error where it refuses.
+// Handed to the saved reference function: whatever the driver marks handOver (a file that is not well-formed or too short, a section beyond one buffer, an
+// unknown curve, an empty entropy, ...). Combines with setup, phase2 and phase2Verify: each replaces its own members of the copy of snarkjs.zKey.
+function installBellman(snarkjs, options) {
+    if (snarkjs.__zkmiBellman) return snarkjs.__zkmiBellman;
+    const bN = require("./groth16_bellman_native.js");
+    const saved = { exportBellman: snarkjs.zKey.exportBellman, bellmanContribute: snarkjs.zKey.bellmanContribute, importBellman: snarkjs.zKey.importBellman };
+    const addon = (options && options.addon) || loadAddon();
+    addon.init(options && options.device !== undefined ? options.device : 0);
+    const dev = options && options.dev;
+    const logOf = (logger) => (level, text) => { if (logger && typeof logger[level] === "function") logger[level](text); };
+    function store(target, raw, what) {
+        if (typeof target === "string") require("fs").writeFileSync(target, raw);
+        else if (target && target.type === "file") require("fs").writeFileSync(target.fileName, raw);
+        else if (target && target.type === "mem") target.data = raw;
+        else throw new Error(what + ": expected a path or a fastfile descriptor for the new file");
+    }
+    // run the driver; null: the call goes to the saved function; false: the reference's logged refusal
+    async function attempt(f, logger) {
+        try { return await f(); } catch (e) {
+            if (!(e instanceof bN.BellmanRefusal)) throw e;
+            if (e.handOver) return null;
+            if (e.returnsFalse) { if (logger) logger.error(e.message); return false; }
+            throw new Error(e.message);
+        }
+    }
+    async function exportBellman(zkeyName, mpcparamsName, logger) {
+        const res = await attempt(() => bN.exportBellman(zkeyName, { addon, dev }), logger);
+        if (res === null) return saved.exportBellman(zkeyName, mpcparamsName, logger);
+        store(mpcparamsName, res.params, "zKey.exportBellman");
+    }
+    async function bellmanContribute(curve, challengeFilename, responseFileName, entropy, logger) {
+        if (!entropy) return saved.bellmanContribute(curve, challengeFilename, responseFileName, entropy, logger);
+        const random64 = new Uint8Array(64);
+        if (globalThis.crypto && globalThis.crypto.getRandomValues) globalThis.crypto.getRandomValues(random64); else require("crypto").randomFillSync(random64);
+        const res = await attempt(() => bN.bellmanContribute(curve, challengeFilename, entropy, { addon, dev, random64, log: logOf(logger) }), logger);
+        // the saved function draws its own 64 bytes: a pinned stream differs from the reference's by this one draw, on calls the driver does not take
+        if (res === null) return saved.bellmanContribute(curve, challengeFilename, responseFileName, entropy, logger);
+        store(responseFileName, res.response, "zKey.bellmanContribute");
+        return res.contributionHash;
+    }
+    async function importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name, logger) {
+        const res = await attempt(() => bN.importBellman(zkeyNameOld, mpcparamsName, name, { addon, dev }), logger);
+        if (res === null) return saved.importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name, logger);
+        if (res === false) return false;
+        store(zkeyNameNew, res.zkey, "zKey.importBellman");
+        return true;
+    }
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, { exportBellman, bellmanContribute, importBellman }));
+    snarkjs.__zkmiBellman = { saved };
+    return snarkjs.__zkmiBellman;
+}
+function uninstallBellman(snarkjs) {
+    if (!snarkjs.__zkmiBellman) return;
+    snarkjs.zKey = Object.freeze(Object.assign({}, snarkjs.zKey, snarkjs.__zkmiBellman.saved));
+    delete snarkjs.__zkmiBellman;
 }
 
 // ---- zKey.verifyFromInit / zKey.verifyFromR1cs on the device (opt-in: registerAll(snarkjs, { phase2Verify: true })) -----------------------------------
@@ -722,4 +785,4 @@ async function uninstallFused(snarkjs) {
     await st.prover.release();
 }
 
-module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, installPtauChallenge, uninstallPtauChallenge, installWtnsCheck, uninstallWtnsCheck, loadAddon };
+module.exports = { register, unregister, registerAll, installFused, uninstallFused, installSetup, uninstallSetup, installPlonkSetup, uninstallPlonkSetup, installFflonkSetup, uninstallFflonkSetup, installPhase2, uninstallPhase2, installPhase2Verify, uninstallPhase2Verify, installBellman, uninstallBellman, installPtauVerify, uninstallPtauVerify, installPtauPrepare, uninstallPtauPrepare, installPtauContribute, uninstallPtauContribute, installPtauChallenge, uninstallPtauChallenge, installWtnsCheck, uninstallWtnsCheck, loadAddon };

@@ -498,6 +498,25 @@ static napi_value js_ptau_import_section(napi_env env, napi_callback_info info) 
     if (rc) return throw_zkmi(env, rc);
     return res;
 }
+/* ---- the H basis change of the Bellman round trip (js/groth16_bellman_native.js)
+ * bellmanHSection(curve, points, logN, direction) -> Uint8Array: direction 0 takes the 2^logN LEM points of section 9 to the 2^logN - 1 U-form H points of a
+ * parameter file, direction 1 takes those back to 2^logN LEM points. */
+static napi_value js_bellman_h_section(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    int32_t curve, log_n, direction;
+    pages_t in;
+    if (get_i32(env, argv[0], &curve) || get_pages(env, argv[1], &in) || get_i32(env, argv[2], &log_n) || log_n < 0 || log_n > 32 || get_i32(env, argv[3], &direction) ||
+        (direction != 0 && direction != 1) || !n8q_of_curve(curve)) BAD_ARG();
+    const size_t sg = 2 * (size_t)n8q_of_curve(curve), n = (size_t)1 << log_n, ob = (direction ? n : n - 1) * sg;
+    uint8_t* out;
+    napi_value res = new_u8(env, ob, &out);
+    if (!res) BAD_ARG();
+    uint8_t* op[1] = {out};
+    const size_t ol[1] = {ob};
+    int rc = ZK_CALL(zkmi_bellman_h_section(curve, as_zk(&in), (unsigned)log_n, direction, op, ol, 1));
+    if (rc) return throw_zkmi(env, rc);
+    return res;
+}
 /* blake2b512Partial(chunks) -> Uint8Array(216): misc.toPartialHash of a fresh hasher after one update per chunk (an array of at most 256 Uint8Arrays) */
 static napi_value js_blake2b512_partial(napi_env env, napi_callback_info info) {
     ARGS(1);
@@ -1498,7 +1517,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
     static const struct { const char* name; napi_callback fn; } fns[] = {
         {"init", js_init}, {"deviceCount", js_device_count}, {"version", js_version}, {"msm", js_msm}, {"releaseBases", js_release_bases},
         {"ntt", js_ntt}, {"frBatch", js_fr_batch}, {"applyKey", js_apply_key}, {"joinABC", js_join_abc}, {"toAffine", js_to_affine}, {"groupFft", js_group_fft}, {"groupApplyKey", js_group_apply_key}, {"groupScale", js_group_scale}, {"sameRatioBatch", js_same_ratio_batch}, {"phase2SectionRatio", js_phase2_section_ratio}, {"phase2HRatio", js_phase2_h_ratio},{"groupConvert", js_group_convert}, {"groth16Setup", js_groth16_setup}, {"plonkSetupLower", js_plonk_setup_lower}, {"plonkSetup", js_plonk_setup}, {"fflonkSetupLower", js_fflonk_setup_lower}, {"fflonkSetup", js_fflonk_setup},
-        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial}, {"ptauChallengeSection", js_ptau_challenge_section}, {"ptauImportSection", js_ptau_import_section}, {"r1csLoad", js_r1cs_load}, {"r1csCheck", js_r1cs_check},
+        {"groth16Prove", js_groth16_prove}, {"groth16ProveAsync", js_groth16_prove_async}, {"msmAsync", js_msm_async}, {"nttAsync", js_ntt_async}, {"groth16Release", js_groth16_release}, {"call", js_call}, {"ptauSectionCheck", js_ptau_section_check}, {"blake2bResume", js_blake2b_resume}, {"ptauLagrangeSection", js_ptau_lagrange_section}, {"ptauContributeSection", js_ptau_contribute_section}, {"blake2b512Partial", js_blake2b512_partial}, {"ptauChallengeSection", js_ptau_challenge_section}, {"ptauImportSection", js_ptau_import_section}, {"bellmanHSection", js_bellman_h_section}, {"r1csLoad", js_r1cs_load}, {"r1csCheck", js_r1cs_check},
         {"groth16Load", js_groth16_load}, {"groth16LoadAsync", js_groth16_load_async}, {"groth16LoadShard", js_groth16_load_shard}, {"groth16Submit", js_groth16_submit},
         {"groth16SubmitAsync", js_groth16_submit_async}, {"groth16Collect", js_groth16_collect}, {"groth16CollectAsync", js_groth16_collect_async},
         {"devAlloc", js_dev_alloc}, {"devFree", js_dev_free}, {"memcpyH2D", js_memcpy_h2d}, {"memcpyD2H", js_memcpy_d2h},

@@ -50,6 +50,7 @@ SYMBOLS = [
     "zkmi_ptau_contribute_section", "zkmi_blake2b512_partial", "zkmi_diag_group_mul_each_dev", "zkmi_diag_set_ptau_slice",
     "zkmi_ptau_challenge_section", "zkmi_ptau_import_section", "zkmi_diag_group2_mul_each_dev",
     "zkmi_r1cs_load", "zkmi_r1cs_check", "zkmi_r1cs_check_dev", "zkmi_r1cs_release", "zkmi_diag_set_r1cs_budget",
+    "zkmi_bellman_h_section", "zkmi_bellman_h_section_dev",
 ]
 
 
@@ -345,6 +346,8 @@ def lib():
     L.zkmi_diag_set_ptau_slice.argtypes = [sz]
     L.zkmi_ptau_challenge_section.argtypes = [C.c_int, C.c_int, Pages, sz, u8p, u8p, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_int]
     L.zkmi_ptau_import_section.argtypes = [C.c_int, C.c_int, Pages, sz] + [C.POINTER(vp), C.POINTER(sz), C.c_int] * 2
+    L.zkmi_bellman_h_section.argtypes = [C.c_int, Pages, C.c_uint, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_int]
+    L.zkmi_bellman_h_section_dev.argtypes = [C.c_int, vp, vp, C.c_uint, C.c_int]
     L.zkmi_diag_group2_mul_each_dev.argtypes = [C.c_int, vp, vp, vp, sz]
     L.zkmi_r1cs_load.argtypes = [C.c_int, Pages, C.c_uint32, C.c_uint32, C.c_uint64]
     L.zkmi_r1cs_check.argtypes = [C.c_uint64, u8p, sz, C.c_uint32, vp]
