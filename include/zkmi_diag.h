@@ -88,6 +88,12 @@ typedef struct zkmi_msm_stage_info {
 } zkmi_msm_stage_info;
 int zkmi_msm_stage_probe_dev(uint64_t table_handle, int curve, int group, const void* d_bases, const void* d_scalars, size_t n, size_t scalar_bytes, uint8_t* buckets,
                              size_t buckets_cap, uint8_t* rowcol, size_t rowcol_cap, uint8_t* result, zkmi_msm_stage_info* info);
+/* Lanes per row / column sum of the last bucket reduction of `group` (1 | 2) in this process, whichever entry point ran it — an MSM, a batch of them, the
+ * probe above, a proof: 8, 16, 32 or 64 for the row / column kernels on unsaturated limbs (rowcol_kernel 0, 1, 2: csrc/msm_select.hpp picks the count from
+ * the launch's shape, or ZKMI_RC_LANES for G1 and ZKMI_RC_LANES_G2 for G2 force it; any other value of a switch makes the reduction fail with
+ * ZKMI_ERR_INVALID), 64 for the generic wave kernel (3), 0 for the staged sums (4) or when the group has not reduced anything yet; -1 for another group.
+ * The info record of the probe does not carry it: its layout is fixed. Host only: a field the driver notes, no launch, copy or synchronisation. */
+int zkmi_msm_rowcol_lanes(int group);
 
 /* Device time (ms, HIP events) of the stages of the last proof, in order: buildABC, 6 NTTs, joinABC, sort(witness),
  * bucket accumulation of MSM B2, B1 (+ the second witness sort), A, C, sort(H scalars), accumulation of MSM H, batched G1 bucket reductions (the B2

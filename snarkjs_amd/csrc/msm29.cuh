@@ -288,38 +288,53 @@ k_msm_accum29(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ i
     else store_xyzz29<C, false>(buckets + (size_t)g * PW, acc, inf);
 }
 
-// Row / column sums of the 2-D bucket reduction (msm.cuh: k_msm_rowcol_wave) over R'-form buckets on unsaturated limbs: one wave per sum, 64
-// lanes add strided shares, then a 6-level tree through LDS in the same launch; the sums leave in the reference's R-form (k_msm_bitsums reads them).
+// Row / column sums of the 2-D bucket reduction (msm.cuh: k_msm_rowcol_wave) over R'-form buckets on unsaturated limbs: LPS lanes per sum (64: one
+// wave per sum; 32, 16, 8: a wave holds 2, 4, 8 sums). Lane t of a block belongs to sum t / LPS of the block and adds the strided share t % LPS,
+// t % LPS + LPS, ... of its row or column; then a tree of log2(LPS) levels through LDS in the same launch, which never leaves the group of LPS lanes;
+// the sums leave in the reference's R-form (k_msm_bitsums reads them). Fewer lanes per sum: fewer tree levels, in which half, a quarter ... of the
+// lanes add while the whole block waits at the barriers, against a longer share per lane (csrc/msm_select.hpp: msm_rowcol_pick chooses).
 // waves per SIMD the register budget is held to: 3 with 9-limb coordinates (168 VGPRs), 2 with 14-limb ones (256)
-template <class C> __global__ void __launch_bounds__(256, Lim29<C>::NL <= 9 ? 3 : 2)
+template <class C, int LPS = 64> __global__ void __launch_bounds__(256, Lim29<C>::NL <= 9 ? 3 : 2)
 k_msm_rowcol_wave29(MsmReduceBatch rb, uint32_t W, uint32_t nb, uint32_t rbits, uint32_t cbits, uint32_t* __restrict__ out) {
+    static_assert(LPS == 64 || LPS == 32 || LPS == 16 || LPS == 8, "lanes per sum");
     constexpr int NL = Lim29<C>::NL, PW = 4 * C::N;
+    constexpr uint32_t SPB = 256 / LPS;                                             // sums per block
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];                  // 256 lanes x 4 NL words
     __shared__ uint32_t inf_s[256];
     const uint32_t Cn = 1u << cbits, R = 1u << rbits;
-    const uint32_t t = threadIdx.x, sub = t & 63u;
+    const uint32_t t = threadIdx.x, sub = t & (uint32_t)(LPS - 1);
     const size_t n_out = (size_t)rb.njobs * W * 2 * Cn;
-    for (size_t blk = blockIdx.x; blk * 4 < n_out; blk += gridDim.x) {
-        const size_t gw = blk * 4 + (t >> 6);                    // sum index: ((job*W + w)*2 + kind)*C + i
+    for (size_t blk = blockIdx.x; blk * SPB < n_out; blk += gridDim.x) {
+        const size_t gw = blk * SPB + t / LPS;                   // sum index: ((job*W + w)*2 + kind)*C + i
         const bool valid = gw < n_out;
         const uint32_t i = (uint32_t)(gw & (Cn - 1)), kind = (uint32_t)(gw >> cbits) & 1u;
         const size_t jw = gw >> (cbits + 1);
         const uint32_t w = (uint32_t)(jw % W), job = (uint32_t)(jw / W);
         XYZZ29<C> acc;
         bool inf = true;
+        if constexpr (LPS < 64) {
+            // SPB <= 32 divides R and Cn (both >= 64): the sums of a block are row slots beyond the row count all together or not at all, and n_out is
+            // a multiple of SPB. Such a block stores its empty sums and takes no part in the tree: the branch is uniform over the block, so every
+            // barrier below is still reached by all of its lanes or by none
+            const size_t g0 = blk * SPB;
+            if (!((g0 >> cbits) & 1u) && (uint32_t)(g0 & (Cn - 1)) >= R) {
+                if (valid && sub == 0) store_xyzz29<C, false>(out + gw * PW, acc, inf);
+                continue;
+            }
+        }
         if (valid) {
             const uint32_t* bk = rb.buckets[job];
             const uint32_t* cn = rb.counts[job];
             const uint32_t cnt = kind ? R : Cn;
             if (!kind && i >= R) { /* row index beyond the row count: empty sum */ }
-            else for (uint32_t e = sub; e < cnt; e += 64) {
+            else for (uint32_t e = sub; e < cnt; e += LPS) {
                 const size_t g = (size_t)w * nb + (kind ? ((size_t)e << cbits) + i : ((size_t)i << cbits) + e);
                 const uint32_t* src = bk + g * PW;
                 if (cn[g] && !xyzz29_words_inf<C>(src)) padd29_ld(acc, inf, [&](int k) { return load29_packed<C>(src + k * C::N); });
             }
         }
         uint32_t* mine = lds + t;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
+        for (uint32_t d = 1; d < LPS; d <<= 1) {
             inf_s[t] = inf ? 1u : 0u;
             if (!inf) {
 #pragma unroll
@@ -1030,19 +1045,21 @@ template <class C> struct Reduce29G2 {
     typedef LdsAcc29<C, T, PACK> Acc;
     static constexpr size_t lds_bytes = (size_t)T * 8 * Acc::EW * 4;
 };
-// one wave per row / column sum over R'-form Fq2 buckets (see k_msm_rowcol_wave29); the sums leave in the reference's R-form
-template <class C> __global__ void __launch_bounds__(Reduce29G2<C>::T, 2)
+// LPS lanes per row / column sum over R'-form Fq2 buckets (see k_msm_rowcol_wave29); the sums leave in the reference's R-form
+template <class C, int LPS = 64> __global__ void __launch_bounds__(Reduce29G2<C>::T, 2)
 k_msm_rowcol_wave29_g2(MsmReduceBatch rb, uint32_t W, uint32_t nb, uint32_t rbits, uint32_t cbits, uint32_t* __restrict__ out) {
+    static_assert(LPS == 64 || LPS == 32 || LPS == 16 || LPS == 8, "lanes per sum");
     constexpr int N = C::N, PW = 8 * N, T = Reduce29G2<C>::T;
+    constexpr uint32_t SPB = T / LPS;                                               // sums per block
     typedef typename Reduce29G2<C>::Acc Acc;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ uint32_t inf_s[T];
     const uint32_t Cn = 1u << cbits, R = 1u << rbits;
-    const uint32_t t = threadIdx.x, sub = t & 63u;
+    const uint32_t t = threadIdx.x, sub = t & (uint32_t)(LPS - 1);
     const size_t n_out = (size_t)rb.njobs * W * 2 * Cn;
     const Acc A{lds + t};
-    for (size_t blk = blockIdx.x; blk * (T / 64) < n_out; blk += gridDim.x) {
-        const size_t gw = blk * (T / 64) + (t >> 6);             // sum index: ((job*W + w)*2 + kind)*C + i
+    for (size_t blk = blockIdx.x; blk * SPB < n_out; blk += gridDim.x) {
+        const size_t gw = blk * SPB + t / LPS;                   // sum index: ((job*W + w)*2 + kind)*C + i
         const bool valid = gw < n_out;
         const uint32_t i = (uint32_t)(gw & (Cn - 1)), kind = (uint32_t)(gw >> cbits) & 1u;
         const size_t jw = gw >> (cbits + 1);
@@ -1051,13 +1068,22 @@ k_msm_rowcol_wave29_g2(MsmReduceBatch rb, uint32_t W, uint32_t nb, uint32_t rbit
         const uint32_t* cn = rb.counts[job];
         const uint32_t cnt = !valid ? 0u : (kind ? R : ((i < R) ? Cn : 0u));
         bool inf = true;
-        for (uint32_t e = sub; e < cnt; e += 64) {
+        if constexpr (LPS < 64) {
+            // a block whose sums are all row slots beyond the row count (SPB <= 32 divides R and Cn: all of them or none, uniform over the block) stores
+            // them and takes no part in the tree; the previous turn of the loop ended at a barrier
+            const size_t g0 = blk * SPB;
+            if (!((g0 >> cbits) & 1u) && (uint32_t)(g0 & (Cn - 1)) >= R) {
+                if (valid && sub == 0) store_xyzz29_lds<C, Acc, false>(out + gw * PW, A, inf);
+                continue;
+            }
+        }
+        for (uint32_t e = sub; e < cnt; e += LPS) {
             const size_t g = (size_t)w * nb + (kind ? ((size_t)e << cbits) + i : ((size_t)i << cbits) + e);
             const uint32_t* src = bk + g * PW;
             if (cn[g] && !xyzz29_words_inf_g2<C>(src))
                 padd29_lds<C>(A, inf, [&](int k, F2x<C>& v) { v.c0 = load29_packed<C>(src + k * 2 * N); v.c1 = load29_packed<C>(src + k * 2 * N + N); });
         }
-        for (uint32_t d = 1; d < 64; d <<= 1) {
+        for (uint32_t d = 1; d < LPS; d <<= 1) {
             inf_s[t] = inf ? 1u : 0u;
             __syncthreads();
             if ((t & (2 * d - 1)) == 0 && !inf_s[t + d]) {

@@ -146,6 +146,9 @@ template <auto Kernel> int lds_opt_in(size_t bytes) {
     return ZKMI_OK;
 }
 static inline int msm_pick_fail(MsmPickError e) { return fail(msm_pick_code(e), msm_pick_message(e)); }
+// zkmi_msm_rowcol_lanes (include/zkmi_diag.h): lanes per row / column sum of the last msm_reduce of G1 | G2 (host bookkeeping like MsmJob::rowcol_kernel, which
+// stays as it is: the probe's info record has no room for it); 0: none yet, or the staged sums
+inline int g_msm_rowcol_lanes[2] = {0, 0};
 
 // ---- stage 4: bucket accumulation for one base table over an existing plan ---------------------------------------------
 // skip: the scalar with index i pairs with base (i - skip); indices < skip are ignored. This lets several MSMs share
@@ -292,29 +295,49 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
     for (int i = 0; i < njobs; i++) all_r29 = all_r29 && jobs[i]->r29;
     for (int i = 0; i < njobs; i++) if (jobs[i]->r29 != jobs[0]->r29) return fail(ZKMI_ERR_INVALID, "msm_reduce: jobs with different bucket formats");
     const int box = !WIDE_R && NL > 9 && all_r29 ? compact_code() : 0;      // as in msm_accumulate: only where a rule reads it
-    const MsmRowcolPick rp = msm_rowcol_pick(WIDE_R ? 2 : 1, NL, all_r29, rbits, cbits, aux, box, msm_tuning());
+    const MsmRowcolPick rp = msm_rowcol_pick(WIDE_R ? 2 : 1, NL, all_r29, rbits, cbits, aux, box, msm_tuning(), n_out);
     if (rp.error != MsmPickError::none) return msm_pick_fail(rp.error);
-    const size_t per_block = rp.threads / 64, rc_blocks = std::min((n_out + per_block - 1) / per_block, rp.max_blocks);
-    auto launch_wave = [&](auto kernel, size_t lds) {         // one wave per sum with the fold inside the launch
+    const size_t per_block = rp.threads / (rp.lanes ? rp.lanes : 64u), rc_blocks = std::min((n_out + per_block - 1) / per_block, rp.max_blocks);
+    auto launch_wave = [&](auto kernel, size_t lds) {         // rp.lanes lanes per sum with the fold inside the launch
         hipLaunchKernelGGL(kernel, dim3((unsigned)rc_blocks), dim3(rp.threads), lds, st, rb, (uint32_t)W, nb, rbits, cbits, rc);
+    };
+    // the instantiation for the picked lanes per sum: f is handed the lane count as a compile-time constant
+    auto with_lanes = [&](auto&& f) {
+        switch (rp.lanes) {
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
+        case 32: return f(std::integral_constant<int, 32>());
+        default: return f(std::integral_constant<int, 64>());
+        }
     };
     switch (rp.kernel) {
     case MsmRowcolKernel::wave29:
     case MsmRowcolKernel::wave29_compact:
         if constexpr (!WIDE_R) {
             constexpr size_t lds29 = (size_t)256 * 4 * NL * 4;
-            ZK_TRY(lds_opt_in<k_msm_rowcol_wave29<Cfg>>(lds29));
-            if constexpr (NL > 9) {
-                ZK_TRY(lds_opt_in<k_msm_rowcol_wave29<Compact<Cfg>>>(lds29));
-                if (rp.kernel == MsmRowcolKernel::wave29_compact) { launch_wave(k_msm_rowcol_wave29<Compact<Cfg>>, lds29); break; }
-            }
-            launch_wave(k_msm_rowcol_wave29<Cfg>, lds29);
+            ZK_TRY(with_lanes([&](auto lps) {
+                constexpr int LPS = decltype(lps)::value;
+                if constexpr (NL > 9) {
+                    if (rp.kernel == MsmRowcolKernel::wave29_compact) {
+                        ZK_TRY((lds_opt_in<k_msm_rowcol_wave29<Compact<Cfg>, LPS>>(lds29)));
+                        launch_wave(k_msm_rowcol_wave29<Compact<Cfg>, LPS>, lds29);
+                        return (int)ZKMI_OK;
+                    }
+                }
+                ZK_TRY((lds_opt_in<k_msm_rowcol_wave29<Cfg, LPS>>(lds29)));
+                launch_wave(k_msm_rowcol_wave29<Cfg, LPS>, lds29);
+                return (int)ZKMI_OK;
+            }));
         }
         break;
     case MsmRowcolKernel::wave29_g2:
         if constexpr (WIDE_R) {
-            ZK_TRY(lds_opt_in<k_msm_rowcol_wave29_g2<Cfg>>(Reduce29G2<Cfg>::lds_bytes));
-            launch_wave(k_msm_rowcol_wave29_g2<Cfg>, Reduce29G2<Cfg>::lds_bytes);
+            ZK_TRY(with_lanes([&](auto lps) {
+                constexpr int LPS = decltype(lps)::value;
+                ZK_TRY((lds_opt_in<k_msm_rowcol_wave29_g2<Cfg, LPS>>(Reduce29G2<Cfg>::lds_bytes)));
+                launch_wave(k_msm_rowcol_wave29_g2<Cfg, LPS>, Reduce29G2<Cfg>::lds_bytes);
+                return (int)ZKMI_OK;
+            }));
         }
         break;
     case MsmRowcolKernel::wave: {
@@ -384,6 +407,7 @@ template <class F> int msm_reduce(MsmJob* const* jobs, int njobs, bool aux = fal
         resA = inA; resR = inR;
         perA = (size_t)2 * W * PW;
     }
+    g_msm_rowcol_lanes[WIDE_R ? 1 : 0] = (int)rp.lanes;
     for (int i = 0; i < njobs; i++) {
         MsmJob& job = *jobs[i];
         job.cbits = (int)cbits;

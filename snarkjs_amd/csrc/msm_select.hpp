@@ -20,6 +20,8 @@ struct MsmTuning {
     bool g2_split_bls = true;       // off: the 14-limb curve alone goes back to the LDS-parked layout
     int aux_rc_sums = 512;          // row / column sums (waves) in flight on the auxiliary stream; <= 0: no cap
     bool multi_overlap = true;      // msm_table_multi: the digit sorts on the auxiliary stream, underneath the previous accumulation
+    int rc_lanes = 0;               // lanes per row / column sum of k_msm_rowcol_wave29: 8, 16, 32 or 64; 0 (not set): msm_rowcol_pick's own choice
+    int rc_lanes_g2 = 0;            // the same for k_msm_rowcol_wave29_g2
 };
 inline const MsmTuning& msm_tuning() {
     static const MsmTuning t = [] {
@@ -34,6 +36,10 @@ inline const MsmTuning& msm_tuning() {
         v.g2_split_bls = on("ZKMI_G2_SPLIT_BLS");
         v.aux_rc_sums = num("ZKMI_AUX_RC_SUMS", 512);
         v.multi_overlap = on("ZKMI_MULTI_OVERLAP");
+        // set to something that is no number, or to 0: -1, which the pick refuses like any other value that is not a lane count
+        auto lanes = [](const char* name) { const char* e = getenv(name); return !e ? 0 : atoi(e) ? atoi(e) : -1; };
+        v.rc_lanes = lanes("ZKMI_RC_LANES");
+        v.rc_lanes_g2 = lanes("ZKMI_RC_LANES_G2");
         return v;
     }();
     return t;
@@ -47,13 +53,16 @@ enum class MsmAccumKernel {
     accum32, accum32_merge, accum32_wide                                 // k_msm_accum<F, false, false | true>, k_msm_accum<F, true, false>
 };
 enum class MsmRowcolKernel { wave29, wave29_compact, wave29_g2, wave, staged };
-enum class MsmPickError { none, merge_g2, merge_r29_target, r29_needs_wave };
-inline int msm_pick_code(MsmPickError e) { return e == MsmPickError::none ? ZKMI_OK : e == MsmPickError::merge_r29_target ? ZKMI_ERR_INVALID : ZKMI_ERR_UNSUPPORTED; }
+enum class MsmPickError { none, merge_g2, merge_r29_target, r29_needs_wave, rc_lanes };
+inline int msm_pick_code(MsmPickError e) {
+    return e == MsmPickError::none ? ZKMI_OK : (e == MsmPickError::merge_r29_target || e == MsmPickError::rc_lanes) ? ZKMI_ERR_INVALID : ZKMI_ERR_UNSUPPORTED;
+}
 inline const char* msm_pick_message(MsmPickError e) {
     switch (e) {
     case MsmPickError::merge_g2: return "msm_accumulate: merge mode is implemented for G1 only";
     case MsmPickError::merge_r29_target: return "msm_accumulate: merge target holds R'-form buckets";
     case MsmPickError::r29_needs_wave: return "msm_reduce: R'-form buckets need the wave row/column sums";
+    case MsmPickError::rc_lanes: return "msm_reduce: ZKMI_RC_LANES / ZKMI_RC_LANES_G2 must be 8, 16, 32 or 64";
     default: return "";
     }
 }
@@ -111,26 +120,45 @@ inline MsmAccumPick msm_accum_pick(int group, int limbs, bool table29, bool merg
 
 struct MsmRowcolPick {
     MsmRowcolKernel kernel;
-    unsigned threads;               // per block; a wave form sums threads / 64 rows or columns per block
+    unsigned threads;               // per block; a wave form sums threads / lanes rows or columns per block
     size_t max_blocks;              // cap on the grid of a wave form (SIZE_MAX: none)
     bool bitsums_lds;               // the plain bit sums of few arrays by k_msm_bitsums_lds instead of k_msm_bitsums
     MsmPickError error;
+    unsigned lanes;                 // per sum: a block of a wave form sums threads / lanes rows or columns (wave29, wave29_compact, wave29_g2: 8, 16, 32 or 64;
+                                    // wave: 64; staged: 0, its lanes per sum follow from the row length in msm_reduce)
 };
-// all_r29: the jobs' buckets hold R'-form words; rbits / cbits: bits of the row / column index; aux: the reduction runs on the auxiliary stream
-inline MsmRowcolPick msm_rowcol_pick(int group, int limbs, bool all_r29, uint32_t rbits, uint32_t cbits, bool aux, int compact_code, const MsmTuning& t) {
+constexpr bool msm_rc_lanes_ok(int v) { return v == 8 || v == 16 || v == 32 || v == 64; }
+// Lanes per row / column sum of the two R'-form wave kernels where no switch forces them. n_sums: the sums of the launch, 2 * 2^cbits per bucket set
+// (0: not known). Measured on one box (profiles/r07_rowcol_lanes_ab.md), BN254 Groth16 at 2^20, c = 20:
+//   G1 (three bucket sets in one launch, main stream): 488 us at 64 lanes, 672 at 32, 817 at 16, 920 at 8, and the headline falls with it (112.5 -> 110.7 ->
+//      108.9 -> 106.6 proofs/s). The launch has 6 144 sums for 3 072 wave slots; fewer lanes make fewer waves than the chip has SIMDs, each with a chain of
+//      37 - 131 dependent additions instead of 22, and nothing else on that stream fills the idle SIMDs. G1 keeps 64, whatever the number of jobs.
+//   G2 on the auxiliary stream (one bucket set, at most aux_rc_sums waves): the kernel itself gets slower too (1.40 ms at 64, 1.69 at 32, 2.24 at 16, 4.58
+//      at 8) but runs underneath the G1 accumulations, which get back the issue slots it no longer takes: 16 lanes gave 114.8 / 114.8 / 114.0 proofs/s
+//      against 113.5 / 112.5 / 112.5 (32: 113.4 - 114.1, 8: 112.7 - 113.0). Measured for the 9-limb curve only; alone on the main stream 64 is the fastest.
+inline unsigned msm_rc_lanes_default(int group, int limbs, uint32_t rbits, uint32_t cbits, bool aux, size_t n_sums) {
+    (void)rbits; (void)cbits; (void)n_sums;
+    return group == 2 && aux && limbs == 9 ? 16u : 64u;
+}
+// all_r29: the jobs' buckets hold R'-form words; rbits / cbits: bits of the row / column index; aux: the reduction runs on the auxiliary stream;
+// n_sums: row and column sums of the launch over all its jobs (0: not known) — read by the lane count alone
+inline MsmRowcolPick msm_rowcol_pick(int group, int limbs, bool all_r29, uint32_t rbits, uint32_t cbits, bool aux, int compact_code, const MsmTuning& t, size_t n_sums = 0) {
     typedef MsmRowcolKernel K;
     const bool wave = t.rowcol_wave && msm_wave_bits(rbits, cbits);
     const bool bitsums_lds = group == 2 && t.rowcol_wave;
-    if (all_r29 && !wave) return {K::staged, 256, SIZE_MAX, bitsums_lds, MsmPickError::r29_needs_wave};
-    if (!wave) return {K::staged, 256, SIZE_MAX, bitsums_lds, MsmPickError::none};
+    if (all_r29 && !wave) return {K::staged, 256, SIZE_MAX, bitsums_lds, MsmPickError::r29_needs_wave, 0};
+    if (!wave) return {K::staged, 256, SIZE_MAX, bitsums_lds, MsmPickError::none, 0};
     const unsigned T = group == 2 ? msm_wide_block(limbs) : 256u;
-    // on the auxiliary stream at most aux_rc_sums sums (waves) are in flight (see k_msm_rowcol_wave), a quarter of the chip's CUs at two
-    // 256-lane blocks per CU; the rest of the CUs stay with the main stream
+    // on the auxiliary stream at most aux_rc_sums waves are in flight (see k_msm_rowcol_wave), a quarter of the chip's CUs at two
+    // 256-lane blocks per CU; the rest of the CUs stay with the main stream. The cap counts waves, however many sums a wave holds
     const size_t max_blocks = aux && t.aux_rc_sums > 0 ? (size_t)t.aux_rc_sums / (T / 64) : SIZE_MAX;
-    if (!all_r29) return {K::wave, T, max_blocks, bitsums_lds, MsmPickError::none};
-    if (group == 2) return {K::wave29_g2, T, max_blocks, bitsums_lds, MsmPickError::none};
+    if (!all_r29) return {K::wave, T, max_blocks, bitsums_lds, MsmPickError::none, 64};
+    const int forced = group == 2 ? t.rc_lanes_g2 : t.rc_lanes;
+    if (forced && !msm_rc_lanes_ok(forced)) return {group == 2 ? K::wave29_g2 : K::wave29, T, max_blocks, bitsums_lds, MsmPickError::rc_lanes, 0};
+    const unsigned lanes = forced ? (unsigned)forced : msm_rc_lanes_default(group, limbs, rbits, cbits, aux, n_sums);
+    if (group == 2) return {K::wave29_g2, T, max_blocks, bitsums_lds, MsmPickError::none, lanes};
     // slow-fetch box, 14-limb curve (254 KB inlined): 5.9 -> 3.0 ms there; BN254's 114 KB kernel gains nothing from the calls (measured)
-    return {limbs == 14 && (compact_code & 4) ? K::wave29_compact : K::wave29, T, max_blocks, bitsums_lds, MsmPickError::none};
+    return {limbs == 14 && (compact_code & 4) ? K::wave29_compact : K::wave29, T, max_blocks, bitsums_lds, MsmPickError::none, lanes};
 }
 
 }  // namespace zkmi

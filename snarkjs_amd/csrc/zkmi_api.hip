@@ -535,6 +535,7 @@ int zkmi_msm_table_release(uint64_t handle) {
 }
 static unsigned long long g_msm_dev_fallbacks = 0;       // zkmi_msm_dev calls that ran on the saturated-limb path for want of scratch memory
 unsigned long long zkmi_msm_dev_fallbacks(void) { return g_msm_dev_fallbacks; }
+int zkmi_msm_rowcol_lanes(int group) { return group == 1 || group == 2 ? g_msm_rowcol_lanes[group - 1] : -1; }
 int zkmi_msm_dev(int curve, int group, const void* d_bases, const void* d_scalars, size_t n, size_t scalar_bytes, uint8_t* out) {
     ZK_TRY(require_ctx());
     ZK_TRY(check_cg(curve, group));

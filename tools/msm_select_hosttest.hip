@@ -4,6 +4,10 @@
 //   accum  group limbs table29 merge into_r29 c compact_code  <8 switches>  ->  kernel threads lanes_per_block lds r29_buckets code [message]
 //   rowcol group limbs all_r29 rbits cbits aux compact_code   <8 switches>  ->  kernel threads max_blocks(-1: none) bitsums_lds code [message]
 //   env                                                                     ->  the 8 fields of msm_tuning(), read from this process's environment
+// and with the lanes per row / column sum (the answers above stay as they were):
+//   rowcol_lanes group limbs all_r29 rbits cbits aux compact_code n_sums  <8 switches> rc_lanes rc_lanes_g2
+//                                                                           ->  kernel threads max_blocks bitsums_lds lanes code [message]
+//   env_lanes                                                               ->  rc_lanes rc_lanes_g2 of msm_tuning()
 #include <stdio.h>
 #include <string.h>
 #include "msm_select.hpp"
@@ -24,9 +28,9 @@ static MsmTuning tuning(const int* v) {
 int main() {
     char line[512], op[16];
     while (fgets(line, sizeof line, stdin)) {
-        int v[15], n = 0, used = 0;
+        int v[18], n = 0, used = 0;
         if (sscanf(line, "%15s%n", op, &used) != 1) continue;
-        for (const char* p = line + used; n < 15; n++) {
+        for (const char* p = line + used; n < 18; n++) {
             int adv = 0;
             if (sscanf(p, "%d%n", &v[n], &adv) != 1) break;
             p += adv;
@@ -41,6 +45,14 @@ int main() {
             const MsmRowcolPick p = msm_rowcol_pick(v[0], v[1], v[2], (uint32_t)v[3], (uint32_t)v[4], v[5], v[6], tuning(v + 7));
             printf("%s %u %lld %d %d %s\n", ROWCOL[(int)p.kernel], p.threads, p.max_blocks == SIZE_MAX ? -1ll : (long long)p.max_blocks, p.bitsums_lds, msm_pick_code(p.error),
                    msm_pick_message(p.error));
+        } else if (!strcmp(op, "env_lanes")) {
+            printf("%d %d\n", msm_tuning().rc_lanes, msm_tuning().rc_lanes_g2);
+        } else if (!strcmp(op, "rowcol_lanes") && n == 18) {
+            MsmTuning t = tuning(v + 8);
+            t.rc_lanes = v[16]; t.rc_lanes_g2 = v[17];
+            const MsmRowcolPick p = msm_rowcol_pick(v[0], v[1], v[2], (uint32_t)v[3], (uint32_t)v[4], v[5], v[6], t, (size_t)v[7]);
+            printf("%s %u %lld %d %u %d %s\n", ROWCOL[(int)p.kernel], p.threads, p.max_blocks == SIZE_MAX ? -1ll : (long long)p.max_blocks, p.bitsums_lds, p.lanes,
+                   msm_pick_code(p.error), msm_pick_message(p.error));
         } else printf("ERR bad request\n");
         fflush(stdout);
     }
